@@ -9,11 +9,15 @@ Other BASELINE configurations (one JSON line each, same fields): --model atomnas
 --shrink 0.3 (config 3: a seeded 30 % of the atoms dead, shrink, steady state on the ragged network; shrink latency reported
 separately), --model atomnas_c_plus --batch 128 (config 5: searched network with SE / Swish / fused blocks).
 
-Rank 0 prints ONE JSON line (contract in the task statement): value = whole-job images/sec, plus
+Rank 0 prints ONE JSON line: value = whole-job images/sec, ms_per_step = wall time of one timed step.  A plain run does only
+that: set-up, warm-up, the timed steps, the line.  --full adds the measurements that take passes of their own:
   roofline     -- the dominant kernel of the step (by summed time), its algorithmic bytes / measured time vs HBM peak,
-                  timed live with events on the launch stream in an eager pass of the same step;
+                  timed live with events on the launch stream in an eager pass of the same step (--no-roofline drops it);
   cpu_baseline -- the CPU oracle (oracle/atomnas_oracle.py, the verified restatement of the reference's step) timed on the
-                  host cores on a bounded sample (N=1 / rank 0 only).
+                  host cores on a bounded sample (N=1 / rank 0 only; --no-cpu-baseline drops it).
+--dump-outputs DIR writes what the last timed step computed (losses, top-k hits, per-sample losses, fixed seeded samples of the
+updated parameters, gradients and EMA shadows, the BatchNorm statistics) as DIR/<name>.npy, so that two builds can be compared
+output for output: with the same arguments the inputs are identical from run to run.
 Weak scaling: every rank trains its own batch of 256; gradients are averaged with one RCCL all-reduce of the flat arena.
 """
 import argparse
@@ -198,6 +202,40 @@ def pmc_mfma_util():
         return None
 
 
+DUMP_SAMPLE = 2 << 20   # elements kept of an arena larger than this (4 B each: five arenas stay well under 64 MB)
+
+
+def dump_outputs(ts, outdir):
+    """What the last timed step handed back, as DIR/<name>.npy: the loss terms, top-k hits and per-sample losses, and the state the
+    step left behind -- parameters, gradients, their EMA shadows, BatchNorm running statistics and theirs.  An arena of more than
+    DUMP_SAMPLE elements is written as a fixed sample (seeded by its length, sorted indices), the same one in every run.
+    Returns {name: number of elements written}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    torch.cuda.synchronize()
+    mgr = ts.mgr
+    arrays = collections.OrderedDict(
+        loss=ts.loss.float(),                      # cross entropy (mean), L2 value, L1 value
+        topk_hits=ts.topk.double(),                # top-1 / top-5 hits on the batch
+        loss_per_sample=ts.loss_vec.float())
+    for name, arena, n in (("params", mgr.P, mgr.nP), ("grads", mgr.G, mgr.nP), ("params_ema", mgr.EMA, mgr.nP),
+                           ("bn_stats", mgr.S, mgr.nS), ("bn_stats_ema", mgr.SEMA, mgr.nS)):
+        if arena is None or n == 0:
+            continue
+        flat = arena.reshape(-1)[:n].float()
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(n).choice(n, DUMP_SAMPLE, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        arrays[name] = flat
+    written = collections.OrderedDict()
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
+
+
 _T0 = time.perf_counter()
 
 
@@ -295,8 +333,12 @@ def main():
                     "then run on the ragged network")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes passes of its own: the per-launch roofline pass and "
+                    "the CPU oracle baseline (off by default: a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-launch roofline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64, fixed seeded samples of the arenas, at most 64 MB in all)")
     ap.add_argument("--input-pipeline", default="resident", choices=["resident", "uint8"], help="resident: the synthetic fp32 batch "
                     "stays in HBM (the headline protocol); uint8: every step takes a fresh batch from the GPU input pipeline -- decoded "
                     "uint8 images from pinned host memory, H2D + crop / PIL-exact resize / flip / normalize on a side stream "
@@ -309,6 +351,8 @@ def main():
     ap.add_argument("--same-device", action="store_true", help="all ranks on cuda:0 (validation of the multi-rank path only)")
     args = ap.parse_args()
 
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -435,7 +479,10 @@ def main():
             rank_ms_per_step=[round(v, 3) for v in rank_ms])
         if shrink_info:
             out["shrink"] = shrink_info
-    if not args.no_roofline and rank == 0:
+    if args.dump_outputs and rank == 0:
+        note("writing the outputs of the last timed step to %s" % args.dump_outputs)
+        out["dumped_outputs"] = dump_outputs(ts, args.dump_outputs)
+    if args.full and not args.no_roofline and rank == 0:
         note("per-launch profile pass")
         agg = kernel_profile(ts, 2 if dtype == torch.bfloat16 else 4, lr0, rho)
         note("profile pass done")
@@ -481,7 +528,7 @@ def main():
                           for k, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])[:8]}
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_guarded(args.model if args.model in ("atomnas_c_supernet", "atomnas_a_supernet", "mobilenet_v2_1.0")
                                                     else "atomnas_c_supernet")
     if rank == 0:
