@@ -22,7 +22,7 @@ from . import transforms as T
 
 DESC_DTYPE = np.dtype([("off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("bi", "<i4"), ("bj", "<i4"), ("bh", "<i4"), ("bw", "<i4"), ("flip", "<i4"),
                        ("pad", "<i4")])   # struct atomnas_img_desc (include/atomnas_hip.h), 40 bytes
-MAX_SCALE = 9.0   # the kernel's tap budget: a crop side may be at most 9x the output side
+MAX_SCALE = 9.0   # the one-pass kernel's tap budget: a crop side above 9x the output side goes through atomnas_image_preprocess_large
 
 
 FILTERS = {"bilinear": 0, "bicubic": 1}   # the `filter` argument of atomnas_image_preprocess: PIL's BILINEAR / BICUBIC resamplers
@@ -38,12 +38,24 @@ def preprocess(pool_dev, desc_dev, n, size, mean, std, out, out_mode=0, stream=N
               ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter], st)
 
 
+def preprocess_large(pool_dev, desc_dev, sel_dev, m, max_rows, size, mean, std, out, workspace, out_mode=0, stream=None, filter="bilinear"):
+    """launches atomnas_image_preprocess_large after preprocess() on the same stream: rewrites the m batch slots listed in sel_dev
+    (int32 device tensor) through the two-pass form; workspace: uint8 device tensor of at least m * max_rows * size * 3 bytes"""
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    mm = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    _lib.call("atomnas_image_preprocess_large", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
+              ctypes.c_void_p(sel_dev.data_ptr()), int(m), int(max_rows), int(size), ctypes.cast(mm, ctypes.c_void_p),
+              ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter],
+              ctypes.c_void_p(workspace.data_ptr()), int(workspace.numel()), st)
+
+
 def check_box(H, W, box, size):
+    """rejects a crop box outside the image; -> True when the box needs the two-pass path (a side above MAX_SCALE x the output)"""
     i, j, h, w = box
     if not (0 <= i and 0 <= j and h > 0 and w > 0 and i + h <= H and j + w <= W):
         raise ValueError("crop box %s outside a %d x %d image" % (box, H, W))
-    if h > MAX_SCALE * size or w > MAX_SCALE * size:
-        raise ValueError("crop box %s is more than %gx the output size %d" % (box, MAX_SCALE, size))
+    return h > MAX_SCALE * size or w > MAX_SCALE * size
 
 
 class DevicePrefetcher(object):
@@ -70,12 +82,14 @@ class DevicePrefetcher(object):
         self.device = torch.cuda.current_device()
         self.max_image_bytes = int(max_image_bytes)
         self.slots = [None, None]   # per slot: (device pool, device descriptors, pinned descriptors, output) sized on first use
+        self.ws = [None, None]      # per slot: workspace of the two-pass path, allocated when a batch first holds an oversize crop box
         # per slot: event behind the last host-to-device copy that READ the slot's pinned descriptors.  The host rewrites them for the
         # batch after next; nothing else orders the host against that copy (the reference's prefetcher never reuses host staging
         # memory), and a caller that does not synchronise per step (graph replay) runs several steps ahead of the device.
         self.desc_read = [None, None]
         self.consumed = [None, None]   # per slot: event on the consumer's stream behind the use of the slot's previous batch
         self.k = 0                     # batches submitted
+        self._done = False             # close() has run
         self.handed = 0                # batches handed out
         self.threaded = bool(threaded)
         if self.threaded:
@@ -93,8 +107,9 @@ class DevicePrefetcher(object):
         s = self.slots[q]
         if s is None or s[0].numel() < nbytes or s[3].shape[0] != n:
             cap = max(nbytes, n * self.max_image_bytes // 4)
-            s = (torch.empty(cap, dtype=torch.uint8, device="cuda"), torch.empty(n * DESC_DTYPE.itemsize, dtype=torch.uint8, device="cuda"),
-                 torch.empty(n * DESC_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
+            # descriptors, then the int32 batch positions of the oversize images (at most n)
+            s = (torch.empty(cap, dtype=torch.uint8, device="cuda"), torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8, device="cuda"),
+                 torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8).pin_memory(),
                  torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device="cuda"))
             self.slots[q] = s
         return s
@@ -114,11 +129,16 @@ class DevicePrefetcher(object):
         ev = self.desc_read[q]
         if ev is not None:
             ev.synchronize()   # the copy queued two batches ago has read desc_pin (normally long done: no wait in steady state)
-        d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE)
+        d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE, count=n)
+        large = []
         for i, (im, box, fl) in enumerate(zip(images, boxes, flips)):
             H, W = int(im.shape[0]), int(im.shape[1])
-            check_box(H, W, box, self.size)
+            if check_box(H, W, box, self.size):
+                large.append(i)
             d[i] = (int(offs[i]), H, W, box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
+        if large:
+            np.frombuffer(desc_pin.numpy(), dtype=np.int32, count=len(large), offset=n * DESC_DTYPE.itemsize)[:] = large
+            max_rows = max(int(boxes[i][2]) for i in large)
         with torch.cuda.stream(self.stream):
             if self.consumed[q] is not None:
                 self.stream.wait_event(self.consumed[q])   # the slot's previous batch has been consumed (handed out two batches ago)
@@ -128,6 +148,12 @@ class DevicePrefetcher(object):
             ev = self.desc_read[q] = self.desc_read[q] or torch.cuda.Event()
             ev.record(self.stream)
             preprocess(pool, desc_dev, n, self.size, self.mean, self.std, out, 0, self.stream, self.filter)
+            if large:   # only batches that hold an oversize crop box pay for the second launch
+                need = len(large) * max_rows * self.size * 3
+                if self.ws[q] is None or self.ws[q].numel() < need:
+                    self.ws[q] = torch.empty(need, dtype=torch.uint8, device="cuda")   # allocated on the side stream that uses it
+                preprocess_large(pool, desc_dev, desc_dev[n * DESC_DTYPE.itemsize:], len(large), max_rows, self.size, self.mean, self.std,
+                                 out, self.ws[q], 0, self.stream, self.filter)
             tgt = target.cuda(non_blocking=True)
             ready = torch.cuda.Event()
             ready.record(self.stream)
@@ -179,10 +205,28 @@ class DevicePrefetcher(object):
         return self._submit()
 
     def close(self):
+        """Safe at any point of the iteration (an evaluation that stops after `bn_calibration_steps` batches): the worker is released,
+        its queue drained so that a blocked put returns, the worker joined, and the side stream's queued copies / launches completed
+        before the slots go back to the allocator."""
+        if getattr(self, "_done", True):
+            return
+        self._done = True
         if self.threaded:
+            import queue
+            import threading
             self._closed = True
             for s in self._free:
                 s.release()
+            if self._thread is not threading.current_thread():
+                while self._thread.is_alive():
+                    try:
+                        self._q.get(timeout=0.01)
+                    except queue.Empty:
+                        pass
+                self._thread.join()
+        self._pending = None
+        self.stream.synchronize()
+        self.slots, self.ws = [None, None], [None, None]
 
     def __del__(self):
         try:

@@ -275,7 +275,8 @@ int atomnas_pack_weights(const float* arena, void* packbuf, const void* jobs_dev
  * pool: the images, packed (3 channels, row pitch 3 W);  desc: device array of N atomnas_img_desc;  S: output side;
  * mean3 / std3: HOST arrays of three floats (read at the call);  out_mode 0: fp32 NCHW [N][3][S][S] (what atomnas_im2col_stem reads),
  * 1: bf16 NHWC with a channel pitch of 8 (padding zero), 2: uint8 [N][S][S][3], the resized and flipped image before ToTensor
- * (parity against PIL).  The crop box must lie inside the image and be at most 9 S on a side (host-side check: utils/dataflow.py). */
+ * (parity against PIL).  The crop box must lie inside the image (host-side check: utils/dataflow.py); this launch handles crop sides of
+ * at most 9 S (the per-pixel tap budget), larger ones go through atomnas_image_preprocess_large afterwards. */
 typedef struct atomnas_img_desc {
   long off;                 /* byte offset of the image in the pool */
   int H, W;                 /* decoded size */
@@ -285,6 +286,14 @@ typedef struct atomnas_img_desc {
 } atomnas_img_desc;
 int atomnas_image_preprocess(const void* pool, const void* desc, int N, int S, const float* mean3, const float* std3, void* out,
                              int out_mode, int filter, void* stream);
+/* The same pixels, bytes and output layouts for crop boxes of any size, in two passes through a uint8 workspace (PIL's structure:
+ * horizontal pass into crop rows x S x 3 bytes, then vertical), the tap weights evaluated on the fly.  Rewrites the batch slots
+ * sel[0 .. M) -- sel: DEVICE array of M positions into desc and out -- after an atomnas_image_preprocess launch over the whole batch on
+ * the same stream.  max_rows: at least the crop height of every selected image;  workspace: at least M x max_rows x S x 3 bytes.
+ * Added without an ABI version change (backwards compatible). */
+int atomnas_image_preprocess_large(const void* pool, const void* desc, const int* sel, int M, int max_rows, int S, const float* mean3,
+                                   const float* std3, void* out, int out_mode, int filter, void* workspace, long workspace_bytes,
+                                   void* stream);
 
 /* ---- deferred fixed-order reductions (ABI 5).  The weight-gradient entry points (atomnas_pw_gemm_tn, atomnas_dwconv_bwd,
  *   atomnas_expand_bwd, atomnas_project_bwd) write per-workgroup partials to their workspace and sum them in a fixed order with one

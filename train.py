@@ -30,14 +30,15 @@ LOADERS = None   # (train_loader, calib_loader, val_loader, test_loader) when th
 
 
 def device_batches(loader, steps):
-    """at most `steps` batches of `loader` through the GPU input pipeline (train.py:215-218 of the reference: DataPrefetcher)"""
+    """at most `steps` batches of `loader` through the GPU input pipeline (train.py:215-218 of the reference: DataPrefetcher);
+    steps=None: every batch of the loader, the short last one included"""
     from atomnas_amd.utils import dataflow
     tf = getattr(getattr(loader, 'dset', None), 'transform', None)   # the split's DeviceTransform: resampling filter, mean, std
     kw = dict(filter=tf.filter, mean=tf.mean, std=tf.std) if isinstance(tf, dataflow.DeviceTransform) else {}
     pre = dataflow.DevicePrefetcher(loader, image_size=cfg.FLAGS.image_size, **kw)
     try:
         for i, (x, y) in enumerate(pre):
-            if i >= steps:
+            if steps is not None and i >= steps:
                 break
             yield x, y
     finally:
@@ -94,6 +95,22 @@ def shrink_model(model_wrapper, ema, optimizer, prune_info, threshold=1e-3, ema_
     logging.info('Current model: {}'.format(mb.output_network(model)))
 
 
+def calibrate_bn(model, epoch):
+    """BN calibration of the eval model (cumulative statistics over `bn_calibration_steps` batches of the calib loader: the train
+    split with the train transforms), then allreduce_bn when distributed (val.py:125-142 of the reference)"""
+    FLAGS = cfg.FLAGS
+    model.eval()
+    model.apply(bn_calibration)
+    with torch.no_grad():
+        calib = (device_batches(LOADERS[1], FLAGS.bn_calibration_steps) if LOADERS is not None and LOADERS[1] is not None else
+                 fake_batches(FLAGS.bn_calibration_per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'],
+                              FLAGS.bn_calibration_steps, 7 + epoch))
+        for x, y in calib:
+            model(x)
+    if FLAGS.use_distributed:
+        udist.allreduce_bn(model)
+
+
 def validate(epoch, model_wrapper, ema, criterion, meters, steps):
     """EMA model -> BN calibration (cumulative statistics) -> evaluation (train.py:419-458), on synthetic batches."""
     import common as mc
@@ -101,16 +118,7 @@ def validate(epoch, model_wrapper, ema, criterion, meters, steps):
     eval_wrapper = mc.get_ema_model(ema, model_wrapper)
     model = mc.unwrap_model(eval_wrapper)
     if FLAGS.get('bn_calibration', False):
-        model.eval()
-        model.apply(bn_calibration)
-        with torch.no_grad():
-            calib = (device_batches(LOADERS[1], FLAGS.bn_calibration_steps) if LOADERS is not None and LOADERS[1] is not None else
-                     fake_batches(FLAGS.bn_calibration_per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'],
-                                  FLAGS.bn_calibration_steps, 7 + epoch))
-            for x, y in calib:
-                model(x)
-        if FLAGS.use_distributed:
-            udist.allreduce_bn(model)
+        calibrate_bn(model, epoch)
     model.eval()
     with torch.no_grad():
         val = (device_batches(LOADERS[2], steps) if LOADERS is not None and LOADERS[2] is not None else
@@ -118,6 +126,67 @@ def validate(epoch, model_wrapper, ema, criterion, meters, steps):
         for x, y in val:
             mc.forward_loss(model, criterion, x, y, meters)
     return meters.flush(), eval_wrapper
+
+
+EVAL_MAX_ACTIVATION_BYTES = 1 << 31
+
+
+def check_eval_size(model, batch):
+    """Refuses a forward whose largest activation tensor (the expanded hidden tensor of a block at its input resolution, or the stem
+    output) reaches 2^31 bytes: the forward / statistics kernels are verified up to the bench step's 1.85 GB tensors, and some of them
+    address a whole tensor with 32-bit byte offsets.  The AtomNAS-C supernet at a calibration batch of 512 (512 x 112^2 x 288 bf16,
+    3.7 GB) is refused; searched networks are far below the limit."""
+    elt = 4 if getattr(model, 'compute_dtype', torch.bfloat16) == torch.float32 else 2
+    res = cfg.FLAGS.image_size // 2   # the stem's stride-2 output
+    worst, where = batch * res * res * ((model.input_channel + 7) // 8 * 8) * elt, 'stem'
+    for name, b in model.get_named_block_list().items():
+        hidden = (sum(b.channels) + 7) // 8 * 8
+        nbytes = batch * res * res * hidden * elt
+        if nbytes > worst:
+            worst, where = nbytes, name
+        res = (res + b.stride - 1) // b.stride
+    if worst >= EVAL_MAX_ACTIVATION_BYTES:
+        raise ValueError('evaluation at batch {}: the hidden tensor of {} is {:.2f} GB, at or above the forward kernels\' limit of '
+                         '2^31 bytes per activation tensor; lower per_gpu_batch_size / bn_calibration_per_gpu_batch_size'.format(
+                             batch, where, worst / 1e9))
+    return worst
+
+
+def evaluate(model_wrapper, ema, epoch=0, phase='test'):
+    """The reference's testing workflow (val.py:109-145, run_one_epoch :17-63): EMA model (if any) -> BN calibration (if
+    `bn_calibration`) -> one pass over the WHOLE test loader, the short last batch included, with per-sample cross entropy (no
+    smoothing) and top-1 / top-5 reduced over ranks.  Distributed, every rank sees the same number of samples: the index list is
+    padded by wrapping around (DistributedSampler, mirrored by DecodedLoader), so a few samples count twice, as in the reference.
+    -> (results, samples counted over all ranks, eval model wrapper)"""
+    import common as mc
+    FLAGS = cfg.FLAGS
+    if LOADERS is None or LOADERS[3] is None:
+        raise ValueError("evaluation needs a test loader: a decoded `dataset` (imagenet1k, imagenet1k_decoded_fake or a module of "
+                         "your own), not {}".format(FLAGS.get('dataset', 'imagenet1k_fake')))
+    eval_wrapper = mc.get_ema_model(ema, model_wrapper)
+    model = mc.unwrap_model(eval_wrapper)
+    check_eval_size(model, max(FLAGS.per_gpu_batch_size, FLAGS.bn_calibration_per_gpu_batch_size if FLAGS.get('bn_calibration', False) else 0))
+    if FLAGS.get('bn_calibration', False):
+        if not FLAGS.use_distributed:
+            logging.warning('Only GPU0 is used when calibration when use DataParallel')
+        calibrate_bn(model, epoch)
+    criterion = optim.CrossEntropyLabelSmooth(FLAGS.model_kwparams['num_classes'], 0.0, reduction='none')
+    meters = mc.get_meters(phase)
+    model.eval()
+    seen = 0
+    with torch.no_grad():
+        for x, y in device_batches(LOADERS[3], None):
+            mc.forward_loss(model, criterion, x, y, meters)
+            seen += x.shape[0]
+    if FLAGS.use_distributed:
+        n = torch.tensor([seen], dtype=torch.float64, device='cuda')
+        torch.distributed.all_reduce(n)
+        seen = int(n.item())
+    results = meters.flush()
+    if udist.is_master():
+        logging.info('Epoch {}/{} {}: '.format(epoch, FLAGS.num_epochs, phase) + ', '.join('{}: {:.4f}'.format(k, v) for k, v in results.items()))
+        logging.info('Epoch {}/{} {} samples: {}, results: {}'.format(epoch, FLAGS.num_epochs, phase, seen, repr(results)))
+    return results, seen, eval_wrapper
 
 
 def load_pretrained(path, model_wrapper, ema):
@@ -173,6 +242,12 @@ def train_val_test():
     ema = mc.setup_ema(model)
     if FLAGS.get('pretrained', None):
         load_pretrained(FLAGS.pretrained, model_wrapper, ema)
+    if FLAGS.get('test_only', False):   # train.py:350-357 of the reference: evaluate, then stop (no optimizer, no step, no checkpoint)
+        if udist.is_master():
+            logging.info('Start testing.')
+        FLAGS._global_step = 0
+        evaluate(model_wrapper, ema)
+        return
     optimizer = optim.get_optimizer(model_wrapper, FLAGS)
     lr_scheduler = optim.get_lr_scheduler(optimizer, FLAGS)
     last_epoch, best_val = -1, 1.0
@@ -247,23 +322,29 @@ def train_val_test():
                     f.write(str(kw))
 
 
+def build_datasets(FLAGS):
+    """(train_set, val_set, test_set) of a decoded source through the reference's factories (train.py:330-339 /
+    utils/dataflow.py:92-267), or None for the synthetic `imagenet1k_fake`"""
+    if FLAGS.get('dataset', 'imagenet1k_fake') == 'imagenet1k_fake':
+        return None
+    from atomnas_amd.utils import dataflow
+    if FLAGS.get('bn_calibration', False):
+        FLAGS._loader_batch_size_calib = FLAGS.bn_calibration_per_gpu_batch_size
+    return dataflow.dataset(*dataflow.data_transforms(FLAGS), FLAGS)
+
+
 def main():
     import common as mc
     FLAGS = cfg.load_app(sys.argv[1:])
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format='%(asctime)s %(message)s')
     global LOADERS
     num_train = NUM_IMAGENET_TRAIN
-    sets = None
-    if FLAGS.get('dataset', 'imagenet1k_fake') != 'imagenet1k_fake':
-        # the reference's three factories (train.py:330-339 / utils/dataflow.py:92-267) over a decoded source
-        from atomnas_amd.utils import dataflow
-        if FLAGS.get('bn_calibration', False):
-            FLAGS._loader_batch_size_calib = FLAGS.bn_calibration_per_gpu_batch_size
-        sets = dataflow.dataset(*dataflow.data_transforms(FLAGS), FLAGS)
-        if sets[0] is not None:
-            num_train = len(sets[0])
+    sets = build_datasets(FLAGS)
+    if sets is not None and sets[0] is not None:
+        num_train = len(sets[0])
     mc.setup_distributed(num_train)
     if sets is not None:
+        from atomnas_amd.utils import dataflow
         LOADERS = dataflow.data_loader(*sets, FLAGS)
     if udist.is_master():
         logging.info(FLAGS)
