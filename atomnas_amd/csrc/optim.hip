@@ -54,6 +54,46 @@ __global__ __launch_bounds__(256) void k_rmsprop_ema(float* __restrict__ p, cons
   }
 }
 
+// SGD with momentum / Nesterov on the same arenas (torch.optim.SGD with dampening 0: buf.mul_(momentum).add_(g');
+// d = nesterov ? g'.add(buf, alpha=momentum) : buf; p.add_(d, alpha=-lr)), with the L2 term, the 1/world scale, the EMA and the L2 value
+// exactly as in k_rmsprop_ema (same launch geometry, same summation order: the L2 value of a given arena is the same bits).
+// buf starts at zero, so the first step gives momentum * 0 + g' = g', torch's first-step `buf = g'`.
+__global__ __launch_bounds__(256) void k_sgd_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                 float* __restrict__ ema, const float* __restrict__ wd_chunk, long n,
+                                                 const float* __restrict__ hyper, float momentum, int nesterov,
+                                                 float* __restrict__ l2_part) {
+#pragma clang fp contract(off)  // keep torch's separate roundings (no fused multiply-add)
+  __shared__ float s_part[4];
+  const float lr = hyper[HYP_LR], d = hyper[HYP_EMA_DECAY], gs = hyper[HYP_GRAD_SCALE];
+  const long nchunks = (n + 255) / 256;
+  float l2acc = 0.f;
+  for (long ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const long i = ch * 256 + threadIdx.x;
+    if (i >= n) continue;
+    const float wd = wd_chunk ? wd_chunk[ch] : 0.f;
+    float pv = p[i];
+    l2acc += (wd * pv) * pv;   // value of the L2 regulariser at the weights this step's loss saw (before the update)
+    float gv = g[i] * gs;
+    gv = gv + wd * pv;
+    float dv = gv;
+    if (buf) {
+      float b = buf[i] * momentum;
+      b = b + gv;
+      buf[i] = b;
+      dv = nesterov ? gv + momentum * b : b;
+    }
+    pv = pv - lr * dv;
+    p[i] = pv;
+    if (ema && d >= 0.f) ema[i] = ema[i] * d + (1.0f - d) * pv;
+  }
+  if (l2_part) {   // per-workgroup partial, fixed order inside the workgroup; summed by k_sum_partials
+    l2acc = wave_sum(l2acc);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = l2acc;
+    __syncthreads();
+    if (threadIdx.x == 0) l2_part[blockIdx.x] = 0.5f * (((s_part[0] + s_part[1]) + s_part[2]) + s_part[3]);
+  }
+}
+
 // one workgroup: out[0] (+)= scale * sum of n values in a fixed order (thread t adds t, t+256, ...; then a fixed tree)
 __global__ __launch_bounds__(256) void k_sum_partials(const float* __restrict__ ws, int n, float scale, int accumulate,
                                                       float* __restrict__ out) {
@@ -136,6 +176,22 @@ extern "C" int atomnas_fused_rmsprop_ema(float* p, const float* g, float* sq, fl
   if (l2_value)
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, 1.f, 0, l2_value);
   return check_launch("fused_rmsprop_ema");
+}
+
+extern "C" int atomnas_fused_sgd_ema(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
+                                     double momentum, int nesterov, float* l2_value, float* ws, void* stream) {
+  ATOMNAS_REQUIRE(p && g && hyper && n > 0, "fused_sgd_ema: bad arguments");
+  ATOMNAS_REQUIRE(!l2_value || (ws && wd_chunk), "fused_sgd_ema: the L2 value needs wd_chunk and a 4096-float workspace");
+  ATOMNAS_REQUIRE(momentum >= 0.0, "fused_sgd_ema: bad hyper-parameters");
+  ATOMNAS_REQUIRE((momentum > 0.0) == (buf != nullptr), "fused_sgd_ema: momentum buffer must be given iff momentum > 0");
+  ATOMNAS_REQUIRE(!nesterov || momentum > 0.0, "fused_sgd_ema: Nesterov momentum needs momentum > 0");
+  long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_sgd_ema, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema, wd_chunk, n, hyper,
+                     (float)momentum, nesterov, l2_value ? ws : nullptr);
+  if (l2_value)
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, 1.f, 0, l2_value);
+  return check_launch("fused_sgd_ema");
 }
 
 // out[0] = scale * sum_i x[i] in a fixed order (mean of the per-sample losses, train.py:178-180 `loss = torch.mean(loss)`)

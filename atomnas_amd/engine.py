@@ -172,18 +172,15 @@ class TrainStep:
             ops.reduce_defer(False)   # flushes on the current stream
 
     def _opt(self):
-        """[gradients summed over ranks] -> + world * rho * penalty * sign(gamma) -> RMSprop on g / world + wd * p (+ EMA of the
-        parameters, L2 value) -> L1 value -> EMA of the BN statistics."""
+        """[gradients summed over ranks] -> + world * rho * penalty * sign(gamma) -> the optimizer's fused launch (RMSprop or SGD) on
+        g / world + wd * p (+ EMA of the parameters, L2 value) -> L1 value -> EMA of the BN statistics."""
         mgr = self.mgr
         rho_ptr = mgr.hyper[ops.HYP_RHO:ops.HYP_RHO + 1]
-        group = self.optimizer.param_groups[0]
         if self._l1 is not None:
             table, njobs = self._l1
             ops.reg_value(mgr.P, table, njobs, 1, rho_ptr, 1.0, self.loss[2:3], ws=self._ws[4096:])
             ops.reg_grad(mgr.P, mgr.G, table, njobs, 1, rho_ptr, mgr.hyper[HYP_SUMMED_RANKS:HYP_SUMMED_RANKS + 1])
-        ops.fused_rmsprop_ema(mgr.P, mgr.G, mgr.SQ, mgr.BUF if group['momentum'] > 0 else None,
-                              mgr.EMA if self.ema is not None else None, self._wd_chunk, mgr.nP, mgr.hyper, group['alpha'],
-                              group['eps'], group['eps_inside_sqrt'], group['momentum'], l2_value=self.loss[1:2], ws=self._ws)
+        self.optimizer.launch_fused(mgr, mgr.EMA if self.ema is not None else None, self._wd_chunk, self.loss[1:2], self._ws)
         if self.ema is not None:
             ops.ema_update(mgr.SEMA, mgr.S, mgr.nS, mgr.hyper)
         ops.add_i64(mgr.step_counter, 1)

@@ -477,6 +477,13 @@ def fused_rmsprop_ema(p, g, sq, buf, ema, wd_chunk, n, hyper, alpha, eps, eps_in
          int(eps_inside_sqrt), float(momentum), _p(l2_value), _p(ws), _stream())
 
 
+def fused_sgd_ema(p, g, buf, ema, wd_chunk, n, hyper, momentum, nesterov, l2_value=None, ws=None):
+    if l2_value is not None and ws is None:
+        ws = torch.empty(4096, dtype=torch.float32, device=p.device)
+    call("atomnas_fused_sgd_ema", _p(p), _p(g), _p(buf), _p(ema), _p(wd_chunk), n, _p(hyper), float(momentum), int(bool(nesterov)),
+         _p(l2_value), _p(ws), _stream())
+
+
 def vec_sum(x, n, scale, out):
     call("atomnas_vec_sum", _p(x), int(n), float(scale), _p(out), _stream())
 

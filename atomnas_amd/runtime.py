@@ -4,7 +4,7 @@ The reference keeps 497 separate parameter tensors, 302 BN buffers, 2x497 RMSpro
 walks them in Python loops every step (utils/optim.py:226-243, utils/rmsprop.py:70-132, utils/optim.py:54-65,
 utils/distributed.py:131-139).  Here every one of those tensors is a *view* into a handful of flat fp32 arenas:
 
-    P    parameters            G    gradients (p.grad)       SQ / BUF   RMSprop square_avg / momentum_buffer
+    P    parameters            G    gradients (p.grad)       SQ / BUF   square_avg (RMSprop) / momentum_buffer (RMSprop, SGD)
     EMA  EMA shadows of P      S    BN running statistics    SEMA       EMA shadows of S         CNT  int64 BN counters
 
 so that the optimizer tail, gradient all-reduce, broadcast and regularisers are O(1) launches on one pointer, while
@@ -367,7 +367,7 @@ class ArenaManager:
         newS = torch.zeros(nS, **f32)
         newC = torch.zeros(nC, dtype=torch.int64, device=dev)
         has_opt = len(self.optimizers) > 0
-        newSQ = torch.zeros(nP, **f32) if has_opt else None
+        newSQ = torch.zeros(nP, **f32) if any(getattr(o, "needs_square_avg", True) for o in self.optimizers) else None
         need_buf = has_opt and any(g["momentum"] > 0 for o in self.optimizers for g in o.param_groups)
         newBUF = torch.zeros(nP, **f32) if need_buf else None
         has_ema = len(self.emas) > 0

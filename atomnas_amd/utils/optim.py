@@ -288,7 +288,7 @@ def get_lr_scheduler(optimizer, FLAGS):
 
 
 def get_optimizer(model, FLAGS):
-    """Optimizer factory (utils/optim.py:309-332); 'rmsprop' is the fused arena optimizer."""
+    """Optimizer factory (utils/optim.py:309-332); 'rmsprop' and 'sgd' are the fused arena optimizers."""
     import importlib
 
     from .rmsprop import RMSprop
@@ -296,7 +296,8 @@ def get_optimizer(model, FLAGS):
         return RMSprop(model.parameters(), lr=FLAGS.lr, alpha=FLAGS.alpha, momentum=FLAGS.momentum, eps=FLAGS.epsilon,
                        eps_inside_sqrt=FLAGS.eps_inside_sqrt, weight_decay=0)
     if FLAGS.optimizer == 'sgd':
-        raise NotImplementedError('SGD is outside the AtomNAS search hot path (apps/slimming/shrink/*.yml use rmsprop)')
+        from .sgd import SGD
+        return SGD(model.parameters(), lr=FLAGS.lr, momentum=FLAGS.momentum, nesterov=FLAGS.nesterov, weight_decay=0)
     try:
         return importlib.import_module(FLAGS.optimizer).get_optimizer(model)
     except ImportError:

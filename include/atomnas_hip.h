@@ -247,6 +247,14 @@ int atomnas_colsum(const void* x, int ld, float* out, long M, int C, int dtype, 
 int atomnas_fused_rmsprop_ema(float* p, const float* g, float* sq, float* buf, float* ema, const float* wd_chunk, long n,
                               const float* hyper, double alpha, double eps, int eps_inside_sqrt, double momentum, float* l2_value,
                               float* ws, void* stream);
+/* SGD with momentum / Nesterov (torch.optim.SGD, dampening 0; utils/optim.py:311-316 `optimizer: sgd`) on the same arenas, with the
+ * conventions of atomnas_fused_rmsprop_ema (hyper vector, wd_chunk per 256 elements, optional ema, optional l2_value + 4096-float ws):
+ *   g' = g*hyper[GRAD_SCALE] + wd_chunk[i/256]*p;  buf = momentum*buf + g';  d = nesterov ? g' + momentum*buf : buf;
+ *   p -= hyper[LR]*d;  ema = dcy*ema + (1-dcy)*p with dcy = hyper[EMA_DECAY] (dcy < 0: skip);  l2_value as above.
+ *   buf == NULL <=> momentum == 0 (d = g').  buf starts at zero: the first step then equals torch's `buf = g'`.
+ * Added without an ABI version change (backwards compatible). */
+int atomnas_fused_sgd_ema(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
+                          double momentum, int nesterov, float* l2_value, float* ws, void* stream);
 /* out[0] = scale * sum_i x[i], fixed summation order: mean of the per-sample losses (train.py:178-180) */
 int atomnas_vec_sum(const float* x, int n, float scale, float* out, void* stream);
 int atomnas_ema_update(float* shadow, const float* x, long n, const float* hyper, void* stream);
