@@ -58,6 +58,9 @@ SIGNATURES = {
     "atomnas_gram": [vp, i32, i64, i32, vp, i64, vp, vp, i32, vp],
     "atomnas_image_preprocess": [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp],
     "atomnas_image_preprocess_large": [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp],
+    "atomnas_image_resize_window": [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp],
+    "atomnas_image_resize_window_large": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp],
+    "atomnas_image_color": [vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp],
     "atomnas_xb_coeffs": [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp],
     "atomnas_fold_jobs": [vp, i32, i32, i64, i64, vp],
 }

@@ -32,6 +32,27 @@ struct ImgDesc {
 };
 static_assert(sizeof(ImgDesc) == 40, "atomnas_img_desc layout");
 
+// second per-image table (atomnas_img_aug): what the window mode and the colour pass need beyond ImgDesc
+struct ImgAug {
+  int oh, ow;        // window mode: the size the WHOLE image is resized to
+  int top, left;     // window mode: corner of the S x S output window inside that resized image
+  int op[3];         // colour pass, in the order applied: 0 none, 1 brightness, 2 contrast (at most one), 3 saturation
+  int pad_;
+  float factor[3];   // blend factor of each op
+  float pad2_;
+  double inc[3];     // Lighting: added to the channels in float64 (0: none)
+};
+static_assert(sizeof(ImgAug) == 72, "atomnas_img_aug layout");
+
+// what is resized to what.  Box mode (WIN = false): the crop box to S x S.  Window mode: the whole image to (oh, ow), of which
+// the output is the S x S window at (top, left): output positions are offset, taps are clamped to the image instead of the box.
+struct PpGeom { int in_w, out_w, x0, in_h, out_h, y0, bi, bj; };
+template <bool WIN>
+__device__ __forceinline__ PpGeom pp_geom(const ImgDesc& d, const ImgAug* __restrict__ aug, int n, int S) {
+  if (WIN) return PpGeom{d.W, aug[n].ow, aug[n].left, d.H, aug[n].oh, aug[n].top, 0, 0};
+  return PpGeom{d.bw, S, 0, d.bh, S, 0, d.bi, d.bj};
+}
+
 constexpr int PP_KMAX = 38;       // taps per dimension: down-scaling up to 9x with the bicubic filter's support of 2 (bilinear: 19)
 constexpr int PP_BITS = 22;       // PRECISION_BITS of Resample.c for 8-bit channels
 
@@ -104,8 +125,9 @@ __device__ __forceinline__ void pp_store(void* __restrict__ out, int n, int S, i
 
 // A workgroup is 64 output columns x 4 output rows of one image: the 64 column and 4 row coefficient sets are computed once (LDS).
 // OUT 0: fp32 NCHW, 1: bf16 NHWC (pitch 8), 2: uint8 NHWC before ToTensor
-template <int OUT>
-__global__ __launch_bounds__(256) void k_image_preprocess(const unsigned char* __restrict__ pool, const ImgDesc* __restrict__ desc, int S,
+template <int OUT, bool WIN>
+__global__ __launch_bounds__(256) void k_image_preprocess(const unsigned char* __restrict__ pool, const ImgDesc* __restrict__ desc,
+                                                         const ImgAug* __restrict__ aug, int S,
                                                          float m0, float m1, float m2, float s0, float s1, float s2,
                                                          void* __restrict__ out, int cubic) {
   __shared__ int s_kx[64][PP_KMAX + 2], s_ky[4][PP_KMAX + 2];   // [..][KMAX] = first sample, [..][KMAX + 1] = count
@@ -114,16 +136,17 @@ __global__ __launch_bounds__(256) void k_image_preprocess(const unsigned char* _
   const int ox = blockIdx.x * 64 + tx;
   const int oy = blockIdx.y * 4 + ty;
   const ImgDesc d = desc[n];
+  const PpGeom g = pp_geom<WIN>(d, aug, n, S);
   if (ty == 0 && ox < S) {
     // the flip mirrors the RESIZED image: output column ox shows resized column S - 1 - ox
     const int rx = d.flip ? S - 1 - ox : ox;
-    pp_coeffs(d.bw, S, rx, cubic, s_kx[tx][PP_KMAX], s_kx[tx][PP_KMAX + 1], s_kx[tx]);
+    pp_coeffs(g.in_w, g.out_w, g.x0 + rx, cubic, s_kx[tx][PP_KMAX], s_kx[tx][PP_KMAX + 1], s_kx[tx]);
   }
-  if (tx == 0 && oy < S) pp_coeffs(d.bh, S, oy, cubic, s_ky[ty][PP_KMAX], s_ky[ty][PP_KMAX + 1], s_ky[ty]);
+  if (tx == 0 && oy < S) pp_coeffs(g.in_h, g.out_h, g.y0 + oy, cubic, s_ky[ty][PP_KMAX], s_ky[ty][PP_KMAX + 1], s_ky[ty]);
   __syncthreads();
   if (ox >= S || oy >= S) return;
   const int xmin = s_kx[tx][PP_KMAX], xn = s_kx[tx][PP_KMAX + 1], ymin = s_ky[ty][PP_KMAX], yn = s_ky[ty][PP_KMAX + 1];
-  const unsigned char* base = pool + d.off + ((long)(d.bi + ymin) * d.W + (d.bj + xmin)) * 3;
+  const unsigned char* base = pool + d.off + ((long)(g.bi + ymin) * d.W + (g.bj + xmin)) * 3;
   const long pitch = (long)d.W * 3;
   int v0 = 1 << (PP_BITS - 1), v1 = v0, v2 = v0;
   for (int y = 0; y < yn; ++y) {
@@ -179,16 +202,20 @@ struct PpWindow {
 };
 
 // horizontal pass: thread (output column ox, crop row r) of image sel[blockIdx.z] -> ws[z][r][ox][3] (columns already in flipped order)
+// (window mode: every row of the image)
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_image_resize_h(const unsigned char* __restrict__ pool, const ImgDesc* __restrict__ desc,
-                                                        const int* __restrict__ sel, int S, int cubic, int max_rows,
-                                                        unsigned char* __restrict__ ws, long ws_pitch) {
+                                                        const ImgAug* __restrict__ aug, const int* __restrict__ sel, int S, int cubic,
+                                                        int max_rows, unsigned char* __restrict__ ws, long ws_pitch) {
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int ox = blockIdx.x * 64 + tx;
   const int r = blockIdx.y * 4 + ty;
-  const ImgDesc d = desc[sel[blockIdx.z]];
-  if (ox >= S || r >= d.bh || d.bh > max_rows) return;   // (the host sizes max_rows: never skipped)
-  const PpWindow w(d.bw, S, d.flip ? S - 1 - ox : ox, cubic);
-  const unsigned char* row = pool + d.off + ((long)(d.bi + r) * d.W + (d.bj + w.lo)) * 3;
+  const int n = sel[blockIdx.z];
+  const ImgDesc d = desc[n];
+  const PpGeom g = pp_geom<WIN>(d, aug, n, S);
+  if (ox >= S || r >= g.in_h || g.in_h > max_rows) return;   // (the host sizes max_rows: never skipped)
+  const PpWindow w(g.in_w, g.out_w, g.x0 + (d.flip ? S - 1 - ox : ox), cubic);
+  const unsigned char* row = pool + d.off + ((long)(g.bi + r) * d.W + (g.bj + w.lo)) * 3;
   int h0 = 1 << (PP_BITS - 1), h1 = h0, h2 = h0;
   for (int x = 0; x < w.cnt; ++x) {
     const int kk = w.k(x);
@@ -201,8 +228,9 @@ __global__ __launch_bounds__(256) void k_image_resize_h(const unsigned char* __r
 }
 
 // vertical pass: thread (ox, oy) of image sel[blockIdx.z] reads its column of the workspace -> the batch slot sel[blockIdx.z] of `out`
-template <int OUT>
-__global__ __launch_bounds__(256) void k_image_resize_v(const ImgDesc* __restrict__ desc, const int* __restrict__ sel, int S, int cubic,
+template <int OUT, bool WIN>
+__global__ __launch_bounds__(256) void k_image_resize_v(const ImgDesc* __restrict__ desc, const ImgAug* __restrict__ aug,
+                                                        const int* __restrict__ sel, int S, int cubic,
                                                         int max_rows, const unsigned char* __restrict__ ws, long ws_pitch, float m0, float m1, float m2,
                                                         float s0, float s1, float s2, void* __restrict__ out) {
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -210,8 +238,9 @@ __global__ __launch_bounds__(256) void k_image_resize_v(const ImgDesc* __restric
   const int oy = blockIdx.y * 4 + ty;
   if (ox >= S || oy >= S) return;
   const int n = sel[blockIdx.z];
-  if (desc[n].bh > max_rows) return;
-  const PpWindow w(desc[n].bh, S, oy, cubic);
+  const PpGeom g = pp_geom<WIN>(desc[n], aug, n, S);
+  if (g.in_h > max_rows) return;
+  const PpWindow w(g.in_h, g.out_h, g.y0 + oy, cubic);
   const unsigned char* col = ws + blockIdx.z * ws_pitch + ((long)w.lo * S + ox) * 3;
   int v0 = 1 << (PP_BITS - 1), v1 = v0, v2 = v0;
   for (int y = 0; y < w.cnt; ++y) {
@@ -224,28 +253,290 @@ __global__ __launch_bounds__(256) void k_image_resize_v(const ImgDesc* __restric
   pp_store<OUT>(out, n, S, oy, ox, pp_clip8(v0), pp_clip8(v1), pp_clip8(v2), m0, m1, m2, s0, s1, s2);
 }
 
+
+// ---------------------------------------------------------------------------------------------------- colour augmentation
+// ColorJitter(brightness, contrast, saturation) in a per-image order, then the PCA Lighting noise, on the resized and flipped uint8
+// image (out_mode 2 of the kernels above), then ToTensor / Normalize through pp_store's arithmetic.  PIL's ImageEnhance restated:
+// every op blends the pixel with a "degenerate" one (black; the mean grey level of the image; the pixel's own grey level) and
+// truncates to uint8, the next op reads that uint8 image.  fp32 product and sum, each rounded (contraction off: the truncation makes
+// one ulp visible).  For 0 <= f <= 1 the blend lies between its two inputs, so the clamp below is the identity there and one
+// expression serves PIL's two branches (truncate / clamp then truncate).
+__device__ __forceinline__ int pp_grey(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }   // PIL's RGB -> L
+
+__device__ __forceinline__ int pp_blend(int d, int p, float f) {
+#pragma clang fp contract(off)
+  const float diff = (float)p - (float)d;
+  const float prod = f * diff;
+  float t = (float)d + prod;
+  t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
+  return (int)t;
+}
+
+__device__ __forceinline__ void pp_color_op(int op, float f, int mean, int& r, int& g, int& b) {
+  if (op == 1) { r = pp_blend(0, r, f); g = pp_blend(0, g, f); b = pp_blend(0, b, f); }
+  else if (op == 2) { r = pp_blend(mean, r, f); g = pp_blend(mean, g, f); b = pp_blend(mean, b, f); }
+  else if (op == 3) { const int l = pp_grey(r, g, b); r = pp_blend(l, r, f); g = pp_blend(l, g, f); b = pp_blend(l, b, f); }
+}
+
+__device__ __forceinline__ int pp_light(int p, double inc) {
+#pragma clang fp contract(off)
+  double t = (double)p + inc;
+  t = t < 0.0 ? 0.0 : (t > 255.0 ? 255.0 : t);
+  return (int)t;
+}
+
+// V consecutive pixels (V = 4: three aligned 32-bit words, S even; V = 1: any S) -> px[3 V]
+template <int V> __device__ __forceinline__ void pp_unpack(const unsigned* w, int* px) {
+#pragma unroll
+  for (int e = 0; e < 3 * V; ++e) px[e] = (w[e >> 2] >> (8 * (e & 3))) & 255;
+}
+template <int V> __device__ __forceinline__ void pp_load_px(const unsigned char* __restrict__ p, int* px) {
+  if (V == 4) {
+    const unsigned* q = reinterpret_cast<const unsigned*>(p);
+    const unsigned w[3] = {q[0], q[1], q[2]};
+    pp_unpack<4>(w, px);
+  } else {
+    px[0] = p[0]; px[1] = p[1]; px[2] = p[2];
+  }
+}
+
+// ops [k0, k1) of the image's list on V pixels
+template <int V> __device__ __forceinline__ void pp_color_ops(const ImgAug& a, int k0, int k1, int mean, int* px) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {   // (static indices: the table stays in scalar registers)
+    if (k < k0 || k >= k1) continue;
+    const int op = a.op[k];
+    const float f = a.factor[k];
+#pragma unroll
+    for (int v = 0; v < V; ++v) pp_color_op(op, f, mean, px[3 * v], px[3 * v + 1], px[3 * v + 2]);
+  }
+}
+
+__device__ __forceinline__ int pp_contrast_at(const ImgAug& a) { return a.op[0] == 2 ? 0 : (a.op[1] == 2 ? 1 : (a.op[2] == 2 ? 2 : 3)); }
+
+// Lighting, then V pixels starting at flat pixel index p0 of image n into `out`
+template <int OUT, int V>
+__device__ __forceinline__ void pp_color_finish(const ImgAug& a, int* px, void* __restrict__ out, int n, int S, long p0, float m0, float m1,
+                                                float m2, float s0, float s1, float s2) {
+  if (a.inc[0] != 0.0 || a.inc[1] != 0.0 || a.inc[2] != 0.0) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      px[3 * v] = pp_light(px[3 * v], a.inc[0]); px[3 * v + 1] = pp_light(px[3 * v + 1], a.inc[1]); px[3 * v + 2] = pp_light(px[3 * v + 2], a.inc[2]);
+    }
+  }
+  if (OUT == 0 && V == 4) {   // the batch the stem reads: one 16-byte store per channel plane (S even: p0 and S * S are multiples of 4)
+    float* o = reinterpret_cast<float*>(out) + (long)n * 3 * S * S + p0;
+    f32x4 c0, c1, c2;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      c0[v] = ((float)px[3 * v] / 255.0f - m0) / s0;
+      c1[v] = ((float)px[3 * v + 1] / 255.0f - m1) / s1;
+      c2[v] = ((float)px[3 * v + 2] / 255.0f - m2) / s2;
+    }
+    *reinterpret_cast<f32x4*>(o) = c0;
+    *reinterpret_cast<f32x4*>(o + (long)S * S) = c1;
+    *reinterpret_cast<f32x4*>(o + 2L * S * S) = c2;
+    return;
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const long p = p0 + v;
+    pp_store<OUT>(out, n, S, (int)(p / S), (int)(p % S), px[3 * v], px[3 * v + 1], px[3 * v + 2], m0, m1, m2, s0, s1, s2);
+  }
+}
+
+// which form atomnas_image_color takes by default (form 0): 1 = two launches, 2 = image in LDS where it fits.  Measured with
+// tools/colorbench.py (input pipeline)
+constexpr int PP_COLOR_DEFAULT_FORM = 2;
+
+// sum over a workgroup of 1024 threads (exact: integers), valid in every thread
+__device__ __forceinline__ int pp_block_sum(int v, int* s_part) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;   // at most 255 * 1024 * 1024: fits
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_part[w];
+  return t;
+}
+
+// PIL's ImageEnhance.Contrast: int(mean of L + 0.5).  In integers: exact, and equal to the float64 form (the mean is a multiple of
+// 1 / npx, never within rounding distance of a half-integer boundary without lying on it)
+__device__ __forceinline__ int pp_mean_level(long sum, long npx) { return (int)((2 * sum + npx) / (2 * npx)); }
+
+// Two-launch form, first launch: one workgroup per image recomputes the ops in front of the contrast on the fly and reduces the grey
+// levels -> means[n] (0 when the image has no contrast op)
+template <int V>
+__global__ __launch_bounds__(1024) void k_color_mean(const unsigned char* __restrict__ src, const ImgAug* __restrict__ aug, int S,
+                                                     int* __restrict__ means) {
+  __shared__ int s_part[16];
+  const int n = blockIdx.x;
+  const ImgAug a = aug[n];
+  const int kc = pp_contrast_at(a);
+  if (kc == 3) {
+    if (threadIdx.x == 0) means[n] = 0;
+    return;
+  }
+  const long npx = (long)S * S;
+  const unsigned char* img = src + (long)n * npx * 3;
+  int sum = 0;
+  for (long p0 = (long)threadIdx.x * V; p0 < npx; p0 += 1024L * V) {
+    int px[3 * V];
+    pp_load_px<V>(img + p0 * 3, px);
+    pp_color_ops<V>(a, 0, kc, 0, px);
+#pragma unroll
+    for (int v = 0; v < V; ++v) sum += pp_grey(px[3 * v], px[3 * v + 1], px[3 * v + 2]);
+  }
+  sum = pp_block_sum(sum, s_part);
+  if (threadIdx.x == 0) means[n] = pp_mean_level(sum, npx);
+}
+
+// second launch: V pixels per thread through the whole chain
+template <int OUT, int V>
+__global__ __launch_bounds__(256) void k_color_apply(const unsigned char* __restrict__ src, const ImgAug* __restrict__ aug,
+                                                     const int* __restrict__ means, int S, float m0, float m1, float m2, float s0, float s1,
+                                                     float s2, void* __restrict__ out) {
+  const int n = blockIdx.y;
+  const long npx = (long)S * S;
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * V;
+  if (p0 >= npx) return;
+  const ImgAug a = aug[n];
+  int px[3 * V];
+  pp_load_px<V>(src + ((long)n * npx + p0) * 3, px);
+  pp_color_ops<V>(a, 0, 3, means[n], px);
+  pp_color_finish<OUT, V>(a, px, out, n, S, p0, m0, m1, m2, s0, s1, s2);
+}
+
+// One-launch form: one workgroup per image keeps the image, as it stands when the contrast runs, in LDS (S * S * 3 bytes: S even
+// and at most 232), so global memory is read once.  Every thread reads back only the words it wrote.
+template <int OUT>
+__global__ __launch_bounds__(1024) void k_color_lds(const unsigned char* __restrict__ src, const ImgAug* __restrict__ aug, int S,
+                                                    float m0, float m1, float m2, float s0, float s1, float s2, void* __restrict__ out) {
+  extern __shared__ unsigned s_img[];
+  __shared__ int s_part[16];
+  const int n = blockIdx.x;
+  const ImgAug a = aug[n];
+  const int kc = pp_contrast_at(a);
+  const long npx = (long)S * S;
+  const unsigned char* img = src + (long)n * npx * 3;
+  int sum = 0;
+  for (long p0 = (long)threadIdx.x * 4; p0 < npx; p0 += 4096) {
+    int px[12];
+    pp_load_px<4>(img + p0 * 3, px);
+    pp_color_ops<4>(a, 0, kc, 0, px);
+    if (kc == 3) {   // no contrast: nothing to wait for
+      pp_color_finish<OUT, 4>(a, px, out, n, S, p0, m0, m1, m2, s0, s1, s2);
+      continue;
+    }
+    unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 12; ++e) w[e >> 2] |= (unsigned)px[e] << (8 * (e & 3));
+    unsigned* q = s_img + (p0 >> 2) * 3;
+    q[0] = w[0]; q[1] = w[1]; q[2] = w[2];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) sum += pp_grey(px[3 * v], px[3 * v + 1], px[3 * v + 2]);
+  }
+  if (kc == 3) return;   // (uniform over the workgroup)
+  const int mean = pp_mean_level(pp_block_sum(sum, s_part), npx);
+  for (long p0 = (long)threadIdx.x * 4; p0 < npx; p0 += 4096) {
+    const unsigned* q = s_img + (p0 >> 2) * 3;
+    const unsigned w[3] = {q[0], q[1], q[2]};
+    int px[12];
+    pp_unpack<4>(w, px);
+    pp_color_ops<4>(a, kc, 3, mean, px);
+    pp_color_finish<OUT, 4>(a, px, out, n, S, p0, m0, m1, m2, s0, s1, s2);
+  }
+}
+
 }  // namespace atomnas
 
 using namespace atomnas;
+
+namespace {
+
+struct PpNorm { float m0, m1, m2, s0, s1, s2; };
+PpNorm pp_norm(const float* mean3, const float* std3) {
+  return PpNorm{mean3 ? mean3[0] : 0.f, mean3 ? mean3[1] : 0.f, mean3 ? mean3[2] : 0.f, std3 ? std3[0] : 1.f, std3 ? std3[1] : 1.f,
+                std3 ? std3[2] : 1.f};
+}
+
+template <bool WIN>
+int launch_one_pass(const char* what, const void* pool, const void* desc, const void* aug, int N, int S, const float* mean3, const float* std3,
+                    void* out, int out_mode, int filter, void* stream) {
+  ATOMNAS_REQUIRE(pool && desc && out && (aug || !WIN) && N > 0 && N <= 65535 && S > 0 && S <= 1024, "%s: bad arguments", what);
+  ATOMNAS_REQUIRE(out_mode == 2 || (mean3 && std3), "%s: mean / std (host arrays of 3 floats) are required", what);
+  ATOMNAS_REQUIRE(out_mode >= 0 && out_mode <= 2, "%s: out_mode %d", what, out_mode);
+  ATOMNAS_REQUIRE(filter == 0 || filter == 1, "%s: filter %d (0 = PIL BILINEAR, 1 = PIL BICUBIC)", what, filter);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((S + 63) / 64, (S + 3) / 4, N), block(256);
+  const ImgDesc* d = reinterpret_cast<const ImgDesc*>(desc);
+  const ImgAug* a = reinterpret_cast<const ImgAug*>(aug);
+  const PpNorm c = pp_norm(mean3, std3);
+  if (out_mode == 2) hipLaunchKernelGGL((k_image_preprocess<2, WIN>), grid, block, 0, st, (const unsigned char*)pool, d, a, S, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out, filter);
+  else if (out_mode == 1) hipLaunchKernelGGL((k_image_preprocess<1, WIN>), grid, block, 0, st, (const unsigned char*)pool, d, a, S, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out, filter);
+  else hipLaunchKernelGGL((k_image_preprocess<0, WIN>), grid, block, 0, st, (const unsigned char*)pool, d, a, S, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out, filter);
+  return check_launch(what);
+}
+
+template <bool WIN>
+int launch_two_pass(const char* what, const void* pool, const void* desc, const void* aug, const int* sel, int M, int max_rows, int S,
+                    const float* mean3, const float* std3, void* out, int out_mode, int filter, void* workspace, long workspace_bytes,
+                    void* stream) {
+  ATOMNAS_REQUIRE(pool && desc && sel && out && workspace && (aug || !WIN) && M > 0 && M <= 65535 && max_rows > 0 && S > 0 && S <= 1024,
+                  "%s: bad arguments", what);
+  ATOMNAS_REQUIRE(out_mode == 2 || (mean3 && std3), "%s: mean / std (host arrays of 3 floats) are required", what);
+  ATOMNAS_REQUIRE(out_mode >= 0 && out_mode <= 2, "%s: out_mode %d", what, out_mode);
+  ATOMNAS_REQUIRE(filter == 0 || filter == 1, "%s: filter %d (0 = PIL BILINEAR, 1 = PIL BICUBIC)", what, filter);
+  const long pitch = (long)max_rows * S * 3;
+  ATOMNAS_REQUIRE((long)M * pitch <= workspace_bytes, "%s: workspace of %ld bytes, %ld needed", what, workspace_bytes, (long)M * pitch);
+  hipStream_t st = (hipStream_t)stream;
+  const ImgDesc* d = reinterpret_cast<const ImgDesc*>(desc);
+  const ImgAug* a = reinterpret_cast<const ImgAug*>(aug);
+  unsigned char* ws = (unsigned char*)workspace;
+  hipLaunchKernelGGL(k_image_resize_h<WIN>, dim3((S + 63) / 64, (max_rows + 3) / 4, M), dim3(256), 0, st, (const unsigned char*)pool, d, a, sel,
+                     S, filter, max_rows, ws, pitch);
+  const dim3 grid((S + 63) / 64, (S + 3) / 4, M), block(256);
+  const PpNorm c = pp_norm(mean3, std3);
+  if (out_mode == 2) hipLaunchKernelGGL((k_image_resize_v<2, WIN>), grid, block, 0, st, d, a, sel, S, filter, max_rows, ws, pitch, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out);
+  else if (out_mode == 1) hipLaunchKernelGGL((k_image_resize_v<1, WIN>), grid, block, 0, st, d, a, sel, S, filter, max_rows, ws, pitch, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out);
+  else hipLaunchKernelGGL((k_image_resize_v<0, WIN>), grid, block, 0, st, d, a, sel, S, filter, max_rows, ws, pitch, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out);
+  return check_launch(what);
+}
+
+template <int OUT>
+int launch_color(const unsigned char* src, const ImgAug* a, int N, int S, const PpNorm& c, void* out, int* means, int form, hipStream_t st) {
+  const long npx = (long)S * S;
+  if (form == 2) {
+    const size_t lds = (size_t)npx * 3;
+    static bool raised = false;   // (per instantiation; a race sets the same attribute twice)
+    if (!raised) {
+      ATOMNAS_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_color_lds<OUT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          160 * 1024 - 256) == hipSuccess, "image_color: the LDS form cannot raise its dynamic LDS limit");
+      raised = true;
+    }
+    hipLaunchKernelGGL(k_color_lds<OUT>, dim3(N), dim3(1024), lds, st, src, a, S, c.m0, c.m1, c.m2, c.s0, c.s1, c.s2, out);
+    return 0;
+  }
+  if (S % 2 == 0) {
+    hipLaunchKernelGGL(k_color_mean<4>, dim3(N), dim3(1024), 0, st, src, a, S, means);
+    hipLaunchKernelGGL((k_color_apply<OUT, 4>), dim3((unsigned)((npx / 4 + 255) / 256), N), dim3(256), 0, st, src, a, means, S, c.m0, c.m1, c.m2,
+                       c.s0, c.s1, c.s2, out);
+  } else {
+    hipLaunchKernelGGL(k_color_mean<1>, dim3(N), dim3(1024), 0, st, src, a, S, means);
+    hipLaunchKernelGGL((k_color_apply<OUT, 1>), dim3((unsigned)((npx + 255) / 256), N), dim3(256), 0, st, src, a, means, S, c.m0, c.m1, c.m2,
+                       c.s0, c.s1, c.s2, out);
+  }
+  return 0;
+}
+
+}  // namespace
 
 // include/atomnas_hip.h: pool = the packed uint8 HWC images, desc = device array of N atomnas_img_desc (ImgDesc above + 4 bytes of padding),
 // out_mode 0: fp32 NCHW, 1: bf16 NHWC (channel pitch 8), 2: uint8 [N][S][S][3] before ToTensor (parity against PIL); filter 0: PIL's BILINEAR,
 // 1: PIL's BICUBIC resampler.
 extern "C" int atomnas_image_preprocess(const void* pool, const void* desc, int N, int S, const float* mean3, const float* std3, void* out,
                                         int out_mode, int filter, void* stream) {
-  ATOMNAS_REQUIRE(pool && desc && out && N > 0 && S > 0 && S <= 1024, "image_preprocess: bad arguments");
-  ATOMNAS_REQUIRE(out_mode == 2 || (mean3 && std3), "image_preprocess: mean / std (host arrays of 3 floats) are required");
-  ATOMNAS_REQUIRE(out_mode >= 0 && out_mode <= 2, "image_preprocess: out_mode %d", out_mode);
-  ATOMNAS_REQUIRE(filter == 0 || filter == 1, "image_preprocess: filter %d (0 = PIL BILINEAR, 1 = PIL BICUBIC)", filter);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((S + 63) / 64, (S + 3) / 4, N), block(256);
-  const ImgDesc* d = reinterpret_cast<const ImgDesc*>(desc);
-  const float m0 = mean3 ? mean3[0] : 0.f, m1 = mean3 ? mean3[1] : 0.f, m2 = mean3 ? mean3[2] : 0.f;
-  const float s0 = std3 ? std3[0] : 1.f, s1 = std3 ? std3[1] : 1.f, s2 = std3 ? std3[2] : 1.f;
-  if (out_mode == 2) hipLaunchKernelGGL(k_image_preprocess<2>, grid, block, 0, st, (const unsigned char*)pool, d, S, m0, m1, m2, s0, s1, s2, out, filter);
-  else if (out_mode == 1) hipLaunchKernelGGL(k_image_preprocess<1>, grid, block, 0, st, (const unsigned char*)pool, d, S, m0, m1, m2, s0, s1, s2, out, filter);
-  else hipLaunchKernelGGL(k_image_preprocess<0>, grid, block, 0, st, (const unsigned char*)pool, d, S, m0, m1, m2, s0, s1, s2, out, filter);
-  return check_launch("image_preprocess");
+  return launch_one_pass<false>("image_preprocess", pool, desc, nullptr, N, S, mean3, std3, out, out_mode, filter, stream);
 }
 
 // include/atomnas_hip.h: the images sel[0 .. M) of the batch (device array of batch positions into desc and out) through the two-pass
@@ -254,24 +545,45 @@ extern "C" int atomnas_image_preprocess(const void* pool, const void* desc, int 
 extern "C" int atomnas_image_preprocess_large(const void* pool, const void* desc, const int* sel, int M, int max_rows, int S,
                                               const float* mean3, const float* std3, void* out, int out_mode, int filter, void* workspace,
                                               long workspace_bytes, void* stream) {
-  ATOMNAS_REQUIRE(pool && desc && sel && out && workspace && M > 0 && M <= 65535 && max_rows > 0 && S > 0 && S <= 1024,
-                  "image_preprocess_large: bad arguments");
-  ATOMNAS_REQUIRE(out_mode == 2 || (mean3 && std3), "image_preprocess_large: mean / std (host arrays of 3 floats) are required");
-  ATOMNAS_REQUIRE(out_mode >= 0 && out_mode <= 2, "image_preprocess_large: out_mode %d", out_mode);
-  ATOMNAS_REQUIRE(filter == 0 || filter == 1, "image_preprocess_large: filter %d (0 = PIL BILINEAR, 1 = PIL BICUBIC)", filter);
-  const long pitch = (long)max_rows * S * 3;
-  ATOMNAS_REQUIRE((long)M * pitch <= workspace_bytes, "image_preprocess_large: workspace of %ld bytes, %ld needed", workspace_bytes,
-                  (long)M * pitch);
+  return launch_two_pass<false>("image_preprocess_large", pool, desc, nullptr, sel, M, max_rows, S, mean3, std3, out, out_mode, filter, workspace,
+                                workspace_bytes, stream);
+}
+
+// include/atomnas_hip.h: window mode (Resize + CenterCrop): aug = device array of N atomnas_img_aug, of which oh / ow / top / left are
+// read; the crop box of desc is not.  One-pass form: H <= 9 oh and W <= 9 ow.
+extern "C" int atomnas_image_resize_window(const void* pool, const void* desc, const void* aug, int N, int S, const float* mean3,
+                                           const float* std3, void* out, int out_mode, int filter, void* stream) {
+  return launch_one_pass<true>("image_resize_window", pool, desc, aug, N, S, mean3, std3, out, out_mode, filter, stream);
+}
+
+// two-pass form of the window mode: max_rows >= the HEIGHT of every selected image (the horizontal pass resizes all its rows)
+extern "C" int atomnas_image_resize_window_large(const void* pool, const void* desc, const void* aug, const int* sel, int M, int max_rows, int S,
+                                                 const float* mean3, const float* std3, void* out, int out_mode, int filter, void* workspace,
+                                                 long workspace_bytes, void* stream) {
+  return launch_two_pass<true>("image_resize_window_large", pool, desc, aug, sel, M, max_rows, S, mean3, std3, out, out_mode, filter, workspace,
+                               workspace_bytes, stream);
+}
+
+// include/atomnas_hip.h: the colour pass.  src: uint8 [N][S][S][3] (out_mode 2 of the resize), aug: device array of N atomnas_img_aug (op /
+// factor / inc are read), means: device scratch of N ints.  form 0: the library's choice, 1: two launches (reduction, then apply),
+// 2: one launch with the image in LDS (S even, S * S * 3 bytes of LDS).
+extern "C" int atomnas_image_color(const void* src, const void* aug, int N, int S, const float* mean3, const float* std3, void* out, int out_mode,
+                                   void* means, int form, void* stream) {
+  ATOMNAS_REQUIRE(src && aug && out && means && N > 0 && N <= 65535 && S > 0 && S <= 1024, "image_color: bad arguments");
+  ATOMNAS_REQUIRE(out_mode == 2 || (mean3 && std3), "image_color: mean / std (host arrays of 3 floats) are required");
+  ATOMNAS_REQUIRE(out_mode >= 0 && out_mode <= 2, "image_color: out_mode %d", out_mode);
+  ATOMNAS_REQUIRE(form >= 0 && form <= 2, "image_color: form %d (0 = default, 1 = two launches, 2 = image in LDS)", form);
+  const bool lds_ok = S % 2 == 0 && (long)S * S * 3 <= 160 * 1024 - 256;
+  ATOMNAS_REQUIRE(form != 2 || lds_ok, "image_color: the LDS form needs an even S with S * S * 3 <= %d bytes (S = %d)", 160 * 1024 - 256, S);
+  if (form == 0) form = PP_COLOR_DEFAULT_FORM == 2 && lds_ok ? 2 : 1;
   hipStream_t st = (hipStream_t)stream;
-  const ImgDesc* d = reinterpret_cast<const ImgDesc*>(desc);
-  unsigned char* ws = (unsigned char*)workspace;
-  hipLaunchKernelGGL(k_image_resize_h, dim3((S + 63) / 64, (max_rows + 3) / 4, M), dim3(256), 0, st, (const unsigned char*)pool, d, sel, S,
-                     filter, max_rows, ws, pitch);
-  const dim3 grid((S + 63) / 64, (S + 3) / 4, M), block(256);
-  const float m0 = mean3 ? mean3[0] : 0.f, m1 = mean3 ? mean3[1] : 0.f, m2 = mean3 ? mean3[2] : 0.f;
-  const float s0 = std3 ? std3[0] : 1.f, s1 = std3 ? std3[1] : 1.f, s2 = std3 ? std3[2] : 1.f;
-  if (out_mode == 2) hipLaunchKernelGGL(k_image_resize_v<2>, grid, block, 0, st, d, sel, S, filter, max_rows, ws, pitch, m0, m1, m2, s0, s1, s2, out);
-  else if (out_mode == 1) hipLaunchKernelGGL(k_image_resize_v<1>, grid, block, 0, st, d, sel, S, filter, max_rows, ws, pitch, m0, m1, m2, s0, s1, s2, out);
-  else hipLaunchKernelGGL(k_image_resize_v<0>, grid, block, 0, st, d, sel, S, filter, max_rows, ws, pitch, m0, m1, m2, s0, s1, s2, out);
-  return check_launch("image_preprocess_large");
+  const PpNorm c = pp_norm(mean3, std3);
+  const unsigned char* s = (const unsigned char*)src;
+  const ImgAug* a = reinterpret_cast<const ImgAug*>(aug);
+  int rc;
+  if (out_mode == 2) rc = launch_color<2>(s, a, N, S, c, out, (int*)means, form, st);
+  else if (out_mode == 1) rc = launch_color<1>(s, a, N, S, c, out, (int*)means, form, st);
+  else rc = launch_color<0>(s, a, N, S, c, out, (int*)means, form, st);
+  if (rc != 0) return rc;
+  return check_launch("image_color");
 }

@@ -22,6 +22,10 @@ from . import transforms as T
 
 DESC_DTYPE = np.dtype([("off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("bi", "<i4"), ("bj", "<i4"), ("bh", "<i4"), ("bw", "<i4"), ("flip", "<i4"),
                        ("pad", "<i4")])   # struct atomnas_img_desc (include/atomnas_hip.h), 40 bytes
+AUG_DTYPE = np.dtype([("oh", "<i4"), ("ow", "<i4"), ("top", "<i4"), ("left", "<i4"), ("op", "<i4", (3,)), ("pad", "<i4"), ("factor", "<f4", (3,)),
+                      ("pad2", "<f4"), ("inc", "<f8", (3,))])   # struct atomnas_img_aug (include/atomnas_hip.h), 72 bytes
+COLOR_OPS = {T.BRIGHTNESS: 1, T.CONTRAST: 2, T.SATURATION: 3}   # atomnas_img_aug.op
+COLOR_FORMS = {"auto": 0, "two_launch": 1, "lds": 2}            # the `form` argument of atomnas_image_color
 MAX_SCALE = 9.0   # the one-pass kernel's tap budget: a crop side above 9x the output side goes through atomnas_image_preprocess_large
 
 
@@ -50,6 +54,71 @@ def preprocess_large(pool_dev, desc_dev, sel_dev, m, max_rows, size, mean, std, 
               ctypes.c_void_p(workspace.data_ptr()), int(workspace.numel()), st)
 
 
+def resize_window(pool_dev, desc_dev, aug_dev, n, size, mean, std, out, out_mode=0, stream=None, filter="bilinear"):
+    """launches atomnas_image_resize_window (Resize + CenterCrop): aug_dev uint8 device tensor holding n AUG_DTYPE records"""
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    _lib.call("atomnas_image_resize_window", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
+              ctypes.c_void_p(aug_dev.data_ptr()), int(n), int(size), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
+              ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter], st)
+
+
+def resize_window_large(pool_dev, desc_dev, aug_dev, sel_dev, m, max_rows, size, mean, std, out, workspace, out_mode=0, stream=None,
+                        filter="bilinear"):
+    """launches atomnas_image_resize_window_large after resize_window() on the same stream (max_rows: the tallest selected IMAGE)"""
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    mm = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    _lib.call("atomnas_image_resize_window_large", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
+              ctypes.c_void_p(aug_dev.data_ptr()), ctypes.c_void_p(sel_dev.data_ptr()), int(m), int(max_rows), int(size),
+              ctypes.cast(mm, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode),
+              FILTERS[filter], ctypes.c_void_p(workspace.data_ptr()), int(workspace.numel()), st)
+
+
+def color(src, aug_dev, n, size, mean, std, out, means, out_mode=0, stream=None, form="auto"):
+    """launches atomnas_image_color: src uint8 [n, size, size, 3] device tensor (out_mode 2 of the resize), aug_dev as above, means an
+    int32 device tensor of at least n elements (scratch)"""
+    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    if src.numel() < n * size * size * 3 or means.numel() < n:
+        raise ValueError("atomnas_image_color: source or scratch buffer too small")
+    _lib.call("atomnas_image_color", ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(aug_dev.data_ptr()), int(n), int(size),
+              ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode),
+              ctypes.c_void_p(means.data_ptr()), COLOR_FORMS[form], st)
+
+
+def fill_aug(rec, aug, box=None, size=None):
+    """writes one AUG_DTYPE record from a transforms.Aug (None: nothing to do); `box` / `size`: the window of a resize decision"""
+    rec["op"], rec["factor"], rec["inc"] = 0, 1.0, 0.0
+    rec["oh"] = rec["ow"] = rec["top"] = rec["left"] = rec["pad"] = 0
+    rec["pad2"] = 0.0
+    if aug is None:
+        return
+    if aug.ops:
+        if len(aug.ops) > 3 or sum(1 for name, _ in aug.ops if name == T.CONTRAST) > 1:
+            raise ValueError("colour decision %r: at most three ops, at most one contrast" % (aug.ops,))
+        for k, (name, f) in enumerate(aug.ops):
+            if name not in COLOR_OPS:
+                raise NotImplementedError("colour op %r (atomnas_image_color: %s)" % (name, ", ".join(COLOR_OPS)))
+            rec["op"][k], rec["factor"][k] = COLOR_OPS[name], f
+    if aug.inc is not None:
+        rec["inc"] = aug.inc
+    if aug.resize is not None:
+        oh, ow = aug.resize
+        top, left, h, w = box
+        if not (oh > 0 and ow > 0 and h == size and w == size and 0 <= top and 0 <= left and top + h <= oh and left + w <= ow):
+            raise ValueError("window %s of side %d outside a resized image of %d x %d" % (box, size, oh, ow))
+        rec["oh"], rec["ow"], rec["top"], rec["left"] = oh, ow, top, left
+
+
+def check_window(H, W, resize):
+    """-> True when resizing the whole H x W image to `resize` = (oh, ow) needs the two-pass path: check_box's rule on the scale"""
+    oh, ow = resize
+    return H > MAX_SCALE * oh or W > MAX_SCALE * ow
+
+
 def check_box(H, W, box, size):
     """rejects a crop box outside the image; -> True when the box needs the two-pass path (a side above MAX_SCALE x the output)"""
     i, j, h, w = box
@@ -62,6 +131,15 @@ class DevicePrefetcher(object):
     """DataPrefetcher (utils/dataflow.py:13-58) for decoded uint8 samples.  `loader` yields batches (images, boxes, flips, targets):
     images = list of uint8 HWC tensors (pinned memory makes the copies asynchronous), boxes = list of (top, left, height, width),
     flips = list of bool, targets = int64 tensor.  Yields (input fp32 [N, 3, S, S] on the GPU, target on the GPU).
+
+    A batch may carry a fifth element, (images, boxes, flips, targets, augs): augs = list of transforms.Aug or None per sample -- what
+    the colour and evaluation transforms of 'imagenet1k_mobile' / 'imagenet1k_inception' decide beyond a box and a flip.  Aug.ops /
+    Aug.inc: ColorJitter's ops in their order and Lighting's increment; the batch is then resized into a per-slot uint8 staging
+    buffer (allocated when the first such batch arrives) and atomnas_image_color writes the fp32 batch from it.  Aug.resize = (oh, ow):
+    the whole image is resized to that and `box` is the S x S window of the RESIZED image (Resize + CenterCrop,
+    atomnas_image_resize_window); all samples of a batch or none.  The table of these decisions (atomnas_img_aug) has per-slot pinned
+    and device buffers of its own under the same reuse rule as the descriptors.  A batch of four elements, or one whose augs are all
+    None, takes exactly the launches and allocations it always took.
 
     The host side of a batch -- drawing it from the loader (the crop / flip decisions of 256 samples), the descriptor table, 256 copy
     submissions: ~7 ms of Python -- runs in a worker thread (threaded=True, default), one batch ahead of the hand-over; the training
@@ -82,6 +160,8 @@ class DevicePrefetcher(object):
         self.device = torch.cuda.current_device()
         self.max_image_bytes = int(max_image_bytes)
         self.slots = [None, None]   # per slot: (device pool, device descriptors, pinned descriptors, output) sized on first use
+        self.aug = [None, None]     # per slot: (device table, pinned table, int32 scratch of the colour pass) once a batch carries augs
+        self.stage = [None, None]   # per slot: uint8 [N, S, S, 3], the resized batch the colour pass reads
         self.ws = [None, None]      # per slot: workspace of the two-pass path, allocated when a batch first holds an oversize crop box
         # per slot: event behind the last host-to-device copy that READ the slot's pinned descriptors.  The host rewrites them for the
         # batch after next; nothing else orders the host against that copy (the reference's prefetcher never reuses host staging
@@ -118,9 +198,13 @@ class DevicePrefetcher(object):
         """draws the next batch and queues its copies and the preprocessing launch on the side stream -> (input, target, ready event)
         or None at the end of the loader"""
         try:
-            images, boxes, flips, target = next(self.loader)
+            batch = next(self.loader)
         except StopIteration:
             return None
+        images, boxes, flips, target = batch[:4]
+        augs = batch[4] if len(batch) > 4 else None
+        if augs is not None and all(a is None for a in augs):
+            augs = None
         q = self.k & 1
         n = len(images)
         sizes = [int(im.numel()) for im in images]
@@ -131,29 +215,65 @@ class DevicePrefetcher(object):
             ev.synchronize()   # the copy queued two batches ago has read desc_pin (normally long done: no wait in steady state)
         d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE, count=n)
         large = []
+        window = augs is not None and any(a is not None and a.resize is not None for a in augs)
+        colour = augs is not None and any(a is not None and (a.ops or a.inc is not None) for a in augs)
+        if window and not all(a is not None and a.resize is not None for a in augs):
+            raise ValueError("a batch mixes resize-window and crop-box samples")
+        if augs is not None:
+            if self.aug[q] is None or self.aug[q][1].numel() < n * AUG_DTYPE.itemsize:
+                self.aug[q] = (torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8, device="cuda"),
+                               torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
+                               torch.empty(n, dtype=torch.int32, device="cuda"))
+            aug_dev, aug_pin, means = self.aug[q]
+            a = np.frombuffer(aug_pin.numpy(), dtype=AUG_DTYPE, count=n)
         for i, (im, box, fl) in enumerate(zip(images, boxes, flips)):
             H, W = int(im.shape[0]), int(im.shape[1])
-            if check_box(H, W, box, self.size):
-                large.append(i)
-            d[i] = (int(offs[i]), H, W, box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
+            if window:
+                if check_window(H, W, augs[i].resize):
+                    large.append(i)
+                box_d = (0, 0, H, W)   # (not read by the window mode)
+            else:
+                if check_box(H, W, box, self.size):
+                    large.append(i)
+                box_d = box
+            d[i] = (int(offs[i]), H, W, box_d[0], box_d[1], box_d[2], box_d[3], 1 if fl else 0, 0)
+            if augs is not None:
+                fill_aug(a[i], augs[i], box, self.size)
         if large:
             np.frombuffer(desc_pin.numpy(), dtype=np.int32, count=len(large), offset=n * DESC_DTYPE.itemsize)[:] = large
-            max_rows = max(int(boxes[i][2]) for i in large)
+            max_rows = max(int(images[i].shape[0]) if window else int(boxes[i][2]) for i in large)
         with torch.cuda.stream(self.stream):
             if self.consumed[q] is not None:
                 self.stream.wait_event(self.consumed[q])   # the slot's previous batch has been consumed (handed out two batches ago)
             for i, im in enumerate(images):
                 pool[int(offs[i]):int(offs[i]) + sizes[i]].copy_(im.reshape(-1), non_blocking=True)
             desc_dev.copy_(desc_pin, non_blocking=True)
+            if augs is not None:
+                aug_dev[:n * AUG_DTYPE.itemsize].copy_(aug_pin[:n * AUG_DTYPE.itemsize], non_blocking=True)   # in front of the event below
             ev = self.desc_read[q] = self.desc_read[q] or torch.cuda.Event()
             ev.record(self.stream)
-            preprocess(pool, desc_dev, n, self.size, self.mean, self.std, out, 0, self.stream, self.filter)
+            dst, mode = out, 0
+            if colour:   # the resize writes uint8 into the staging buffer, the colour pass the batch
+                if self.stage[q] is None or self.stage[q].numel() < n * self.size * self.size * 3:
+                    self.stage[q] = torch.empty(n * self.size * self.size * 3, dtype=torch.uint8, device="cuda")
+                dst, mode = self.stage[q], 2
+            if window:
+                resize_window(pool, desc_dev, aug_dev, n, self.size, self.mean, self.std, dst, mode, self.stream, self.filter)
+            else:
+                preprocess(pool, desc_dev, n, self.size, self.mean, self.std, dst, mode, self.stream, self.filter)
             if large:   # only batches that hold an oversize crop box pay for the second launch
                 need = len(large) * max_rows * self.size * 3
                 if self.ws[q] is None or self.ws[q].numel() < need:
                     self.ws[q] = torch.empty(need, dtype=torch.uint8, device="cuda")   # allocated on the side stream that uses it
-                preprocess_large(pool, desc_dev, desc_dev[n * DESC_DTYPE.itemsize:], len(large), max_rows, self.size, self.mean, self.std,
-                                 out, self.ws[q], 0, self.stream, self.filter)
+                sel = desc_dev[n * DESC_DTYPE.itemsize:]
+                if window:
+                    resize_window_large(pool, desc_dev, aug_dev, sel, len(large), max_rows, self.size, self.mean, self.std, dst, self.ws[q],
+                                        mode, self.stream, self.filter)
+                else:
+                    preprocess_large(pool, desc_dev, sel, len(large), max_rows, self.size, self.mean, self.std, dst, self.ws[q], mode,
+                                     self.stream, self.filter)
+            if colour:
+                color(dst, aug_dev, n, self.size, self.mean, self.std, out, means, 0, self.stream)
             tgt = target.cuda(non_blocking=True)
             ready = torch.cuda.Event()
             ready.record(self.stream)
@@ -226,7 +346,7 @@ class DevicePrefetcher(object):
                 self._thread.join()
         self._pending = None
         self.stream.synchronize()
-        self.slots, self.ws = [None, None], [None, None]
+        self.slots, self.ws, self.aug, self.stage = [None, None], [None, None], [None, None], [None, None]
 
     def __del__(self):
         try:
@@ -244,19 +364,25 @@ class DevicePrefetcher(object):
 class SyntheticDecodedImages(object):
     """A stand-in for the decoded ImageNet samples of the reference's loaders (utils/dataflow.py:173-236; JPEG / LMDB are out of scope):
     `pool_size` uint8 HWC images of ImageNet-like sizes in pinned memory, batches of `batch` samples with the boxes and flips of the
-    'imagenet1k_mnas_bilinear' training transform (random.seed(seed) fixes them)."""
+    'imagenet1k_mnas_bilinear' training transform (random.seed(seed) fixes them).  transform: a DeviceTransform of data_transforms
+    instead; one that decides more than (box, flip) makes the batches five elements long (DevicePrefetcher), and its numpy draws
+    (Lighting) come from a stream seeded the same way."""
     SIZES = [(375, 500), (500, 375), (333, 500), (480, 640), (500, 500), (256, 341), (600, 400), (224, 224)]
 
-    def __init__(self, batch, steps, num_classes=1000, image_size=224, pool_size=64, seed=0, train=True):
+    def __init__(self, batch, steps, num_classes=1000, image_size=224, pool_size=64, seed=0, train=True, transform=None):
         g = torch.Generator().manual_seed(seed)
+        self.pin = torch.cuda.is_available()   # (host logic runs without a GPU)
         self.images = []
         for q in range(pool_size):
             H, W = self.SIZES[q % len(self.SIZES)]
-            self.images.append(torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, generator=g).pin_memory())
+            im = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, generator=g)
+            self.images.append(im.pin_memory() if self.pin else im)
         self.batch, self.steps, self.num_classes = batch, steps, num_classes
         self.rng_state = random.Random(seed).getstate()
         tr, va = T.mnas_bilinear_transforms(image_size)
         self.crop, self.flip = tr if train else va
+        self.transform = transform
+        self.np_state = np.random.RandomState(seed).get_state() if transform is not None else None
         self.g = g
 
     def __len__(self):
@@ -269,12 +395,25 @@ class SyntheticDecodedImages(object):
             for _ in range(self.steps):
                 idx = [random.randrange(len(self.images)) for _ in range(self.batch)]
                 imgs = [self.images[i] for i in idx]
-                boxes = [self.crop(im) for im in imgs]
-                flips = [bool(self.flip()) if self.flip is not None else False for _ in imgs]
-                target = torch.randint(0, self.num_classes, (self.batch,), generator=self.g).pin_memory()
+                if self.transform is not None:
+                    np_saved = np.random.get_state()
+                    np.random.set_state(self.np_state)
+                    try:
+                        dec = [self.transform(im) for im in imgs]
+                    finally:
+                        self.np_state = np.random.get_state()
+                        np.random.set_state(np_saved)
+                    extra = ([d[2] for d in dec],) if any(len(d) > 2 for d in dec) else ()
+                    boxes, flips = [d[0] for d in dec], [d[1] for d in dec]
+                else:
+                    extra = ()
+                    boxes = [self.crop(im) for im in imgs]
+                    flips = [bool(self.flip()) if self.flip is not None else False for _ in imgs]
+                target = torch.randint(0, self.num_classes, (self.batch,), generator=self.g)
+                target = target.pin_memory() if self.pin else target
                 self.rng_state = random.getstate()
                 random.setstate(saved)
-                yield imgs, boxes, flips, target
+                yield (imgs, boxes, flips, target) + extra
                 saved = random.getstate()
                 random.setstate(self.rng_state)
         finally:
@@ -285,7 +424,8 @@ class SyntheticDecodedImages(object):
 # data_transforms / dataset / data_loader (utils/dataflow.py:92-267): same names, signatures and FLAGS keys, so that
 # `train.py app:<yml>` reaches the GPU input pipeline from the yaml.  What differs is WHERE the pixel work happens: a transform here
 # only decides (crop box, flip) per sample, the dataset hands out decoded uint8 images with those decisions, and DevicePrefetcher
-# runs crop / resize / flip / ToTensor / Normalize in one kernel per batch.  'imagenet1k' decodes image folders with PIL on loader
+# runs crop / resize / flip / ToTensor / Normalize in one kernel per batch ('imagenet1k_mobile' / 'imagenet1k_inception': a uint8 resize,
+# then ColorJitter / Lighting / ToTensor / Normalize in atomnas_image_color; evaluation: Resize + CenterCrop in window mode).  'imagenet1k' decodes image folders with PIL on loader
 # threads; 'imagenet1k_lmdb' raises (no lmdb module in this image).
 class DeviceTransform(object):
     """What data_transforms returns per split: the deciders of a transform chain whose pixel work is atomnas_image_preprocess.
@@ -302,6 +442,33 @@ class DeviceTransform(object):
         return "DeviceTransform({}, {}, size={})".format(self.crop, self.flip, self.size)
 
 
+class ColorDeviceTransform(DeviceTransform):
+    """The deciders of 'imagenet1k_mobile' / 'imagenet1k_inception'.  transform(img) -> (box, flip, transforms.Aug): three elements, so
+    datasets and loaders pass the Aug along as the fifth element of a batch.  Training (crop, jitter, lighting, flip): the draws
+    come in the reference's Compose order -- RandomResizedCrop, ColorJitter, Lighting (numpy's global generator), flip -- in the
+    calling thread.  Evaluation (resize, crop): Resize(256) + CenterCrop(size), the box is a window of the resized image."""
+
+    def __init__(self, crop, flip, size, mean, std, filter="bilinear", jitter=None, lighting=None, resize=None):
+        DeviceTransform.__init__(self, crop, flip, size, mean, std, filter)
+        self.jitter, self.lighting, self.resize = jitter, lighting, resize
+
+    def __call__(self, img):
+        if self.resize is not None:
+            oh, ow = self.resize.get_size(img)
+            if oh < self.size or ow < self.size:
+                raise NotImplementedError("CenterCrop(%d) of an image resized to %d x %d would pad" % (self.size, oh, ow))
+            box, win = self.crop((ow, oh)), (oh, ow)
+        else:
+            box, win = self.crop(img), None
+        ops = self.jitter.get_params() if self.jitter is not None else None
+        inc = self.lighting.get_inc() if self.lighting is not None else None
+        flip = bool(self.flip()) if self.flip is not None else False
+        return box, flip, T.Aug(ops or None, inc, win)
+
+    def __repr__(self):
+        return "ColorDeviceTransform({}, {}, {}, {}, {}, size={})".format(self.resize, self.crop, self.jitter, self.lighting, self.flip, self.size)
+
+
 def data_transforms(FLAGS):
     """Get transform of dataset (utils/dataflow.py:92-170) -> (train_transforms, val_transforms, test_transforms)."""
     name = FLAGS.data_transforms
@@ -312,8 +479,20 @@ def data_transforms(FLAGS):
         train = DeviceTransform(crop, flip, size, T.IMAGENET_MEAN, T.IMAGENET_STD, filt)
         val = DeviceTransform(vcrop, None, size, T.IMAGENET_MEAN, T.IMAGENET_STD, filt)
         return train, val, val
-    if name in ('imagenet1k_basic', 'imagenet1k_inception', 'imagenet1k_mobile'):
-        raise NotImplementedError("data_transforms '{}': ColorJitter / Lighting have no device kernel here".format(name))
+    if name in ('imagenet1k_inception', 'imagenet1k_mobile'):
+        size = int(FLAGS.get('image_size', 224)) if hasattr(FLAGS, 'get') else 224
+        if name == 'imagenet1k_inception':
+            mean, std, crop_scale = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), 0.08
+        else:
+            mean, std, crop_scale = T.IMAGENET_MEAN, T.IMAGENET_STD, 0.25
+        (crop, jitter, lighting, flip), (resize, vcrop) = T.color_transforms(size, crop_scale, jitter=0.4, lighting=0.1)
+        train = ColorDeviceTransform(crop, flip, size, mean, std, "bilinear", jitter=jitter, lighting=lighting)
+        val = ColorDeviceTransform(vcrop, None, size, mean, std, "bilinear", resize=resize)
+        return train, val, val
+    if name == 'imagenet1k_basic':
+        raise NotImplementedError("data_transforms 'imagenet1k_basic': the chain of 'imagenet1k_mobile' with crop_scale 0.08, which the kernels "
+                                  "cover; the name is still refused because tests/test_input_pipeline.py pins the refusal -- lifting it is "
+                                  "left to a follow-up")
     try:
         transforms_lib = importlib.import_module(name)
         return transforms_lib.data_transforms()
@@ -340,7 +519,8 @@ class FakeData(object):
 
 class DecodedFakeData(object):
     """`size` decoded samples for the GPU input pipeline: a pool of uint8 HWC images of ImageNet-like sizes in pinned memory (sample i
-    is image i mod pool) with seeded labels; __getitem__ applies the split's DeviceTransform and returns (image, box, flip, target).
+    is image i mod pool) with seeded labels; __getitem__ applies the split's DeviceTransform and returns (image, box, flip, target), or
+    (image, box, flip, aug, target) when the transform decides more (ColorDeviceTransform).
     Stand-in for ImageFolder / ImageFolderLMDB + a JPEG decoder, which this image cannot provide."""
 
     def __init__(self, size, transform, num_classes=1000, pool_size=64, seed=0):
@@ -364,8 +544,7 @@ class DecodedFakeData(object):
 
     def __getitem__(self, index):
         im, target = self.load(index)
-        box, flip = self.transform(im)
-        return im, box, flip, target
+        return (im,) + tuple(self.transform(im)) + (target,)   # (image, box, flip[, aug], target)
 
 
 IMG_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp', '.pgm', '.tif', '.tiff', '.webp')   # torchvision.datasets.folder
@@ -376,7 +555,7 @@ class ImageFolderDecoded(object):
     `root/<class>/<file>` with the classes sorted by name (class index = position) and the files of a class sorted by path; `load(i)`
     decodes with PIL (`Image.open(path).convert('RGB')`, what torchvision's default loader does) into a uint8 HWC tensor (pinned when a
     GPU is present) -- the decode releases the GIL, so DecodedLoader runs it on `data_loader_workers` threads --, `__getitem__` adds the
-    split's DeviceTransform decisions: (image, box, flip, target).  The pixel work of the transform stays on the GPU."""
+    split's DeviceTransform decisions: (image, box, flip[, aug], target).  The pixel work of the transform stays on the GPU."""
 
     def __init__(self, root, transform):
         import os
@@ -409,8 +588,7 @@ class ImageFolderDecoded(object):
 
     def __getitem__(self, index):
         im, target = self.load(index)
-        box, flip = self.transform(im)
-        return im, box, flip, target
+        return (im,) + tuple(self.transform(im)) + (target,)   # (image, box, flip[, aug], target)
 
 
 def dataset(train_transforms, val_transforms, test_transforms, FLAGS):
@@ -441,12 +619,12 @@ def dataset(train_transforms, val_transforms, test_transforms, FLAGS):
 
 class DecodedLoader(object):
     """torch.utils.data.DataLoader's role for decoded samples (utils/dataflow.py:217-225 `_build_loader`): batches of `batch_size`
-    samples (image, box, flip, target) -> (images, boxes, flips, targets int64 pinned), the form DevicePrefetcher takes.  shuffle:
+    samples (image, box, flip[, aug], target) -> (images, boxes, flips, targets int64 pinned[, augs]), the form DevicePrefetcher takes.  shuffle:
     a fresh seeded permutation per pass; rank / world: the DistributedSampler split (every rank the same number of samples, the
     index list padded by wrapping around); drop_last as torch's.  workers > 0: the samples of a batch are LOADED (decoded) on that many
     threads (PIL's decoder releases the GIL); the transform's random decisions are then drawn in sample order by the iterating thread
-    (one stream of Python's `random`, whatever the thread timing) -- with DevicePrefetcher that is its worker thread, off the training
-    thread."""
+    (one stream of Python's `random` -- and of numpy's global generator, which Lighting draws from -- whatever the thread timing)
+    -- with DevicePrefetcher that is its worker thread, off the training thread."""
 
     def __init__(self, dset, batch_size, shuffle, rank=0, world=1, drop_last=False, seed=0, workers=0):
         self.dset, self.batch_size, self.shuffle = dset, int(batch_size), bool(shuffle)
@@ -484,12 +662,12 @@ class DecodedLoader(object):
                 loaded = list(self._pool.map(self.dset.load, chunk))
                 samples = []
                 for im, tgt in loaded:
-                    box, flip = self.dset.transform(im)
-                    samples.append((im, box, flip, tgt))
+                    samples.append((im,) + tuple(self.dset.transform(im)) + (tgt,))
             else:
                 samples = [self.dset[i] for i in chunk]
-            target = torch.tensor([s[3] for s in samples], dtype=torch.int64)
-            yield [s[0] for s in samples], [s[1] for s in samples], [s[2] for s in samples], (target.pin_memory() if pin else target)
+            target = torch.tensor([s[-1] for s in samples], dtype=torch.int64)
+            extra = ([s[3] if len(s) > 4 else None for s in samples],) if any(len(s) > 4 for s in samples) else ()
+            yield ([s[0] for s in samples], [s[1] for s in samples], [s[2] for s in samples], (target.pin_memory() if pin else target)) + extra
 
 
 def data_loader(train_set, val_set, test_set, FLAGS):

@@ -6,9 +6,17 @@ consumption (Python's `random`, in the reference's order), so a seeded run draws
 
 torchvision is not installed in this image, so the reference module cannot be imported; the known answers of tests/test_input_pipeline.py
 are computed from the reference's formulas transcribed there, independently of this file.
+
+The chain of 'imagenet1k_mobile' / 'imagenet1k_inception' (utils/dataflow.py:92-131) is decided the same way: torchvision's
+RandomResizedCrop, ColorJitter (brightness, contrast, saturation), the reference's Lighting (utils/transforms.py:21-51), and for
+evaluation Resize + CenterCrop.  Their pixel work is atomnas_image_color / atomnas_image_resize_window; the known answers are in
+tests/test_color_transforms.py.
 """
+import collections
 import math
 import random
+
+import numpy as np
 
 
 def _size_of(img):
@@ -152,6 +160,169 @@ class RandomHorizontalFlip(object):
 
     def __call__(self, img=None):
         return random.random() < self.p
+
+
+class RandomResizedCrop(object):
+    """torchvision.transforms.RandomResizedCrop's box: an area fraction from `scale` and a log-uniform aspect ratio from `ratio`, ten
+    attempts, then the central crop of the nearest allowed aspect ratio.  get_params draws random.uniform (area), random.uniform (log
+    ratio) per attempt and random.randint (top), random.randint (left) on success, in that order."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), interpolation=None):
+        self.size = size if isinstance(size, tuple) else (size, size)
+        if interpolation is not None and _interp_name(interpolation) not in ("bilinear", "bicubic"):
+            raise NotImplementedError("atomnas_image_preprocess resizes with PIL's BILINEAR or BICUBIC filter only (got %r)" % (interpolation,))
+        self.filter = _interp_name(interpolation) if interpolation is not None else "bilinear"   # torchvision's default
+        self.scale, self.ratio = tuple(scale), tuple(ratio)
+
+    def get_params(self, img):
+        width, height = _size_of(img)
+        area = width * height
+        for _ in range(10):
+            target_area = random.uniform(self.scale[0], self.scale[1]) * area
+            aspect_ratio = math.exp(random.uniform(math.log(self.ratio[0]), math.log(self.ratio[1])))
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if 0 < w <= width and 0 < h <= height:   # (a zero-sized box never reaches the kernel)
+                i = random.randint(0, height - h)
+                j = random.randint(0, width - w)
+                return i, j, h, w
+        in_ratio = width / height
+        if in_ratio < min(self.ratio):
+            w = width
+            h = int(round(w / min(self.ratio)))
+        elif in_ratio > max(self.ratio):
+            h = height
+            w = int(round(h * max(self.ratio)))
+        else:
+            w, h = width, height
+        return (height - h) // 2, (width - w) // 2, h, w
+
+    __call__ = get_params
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(size={0}, scale={1}, ratio={2})'.format(
+            self.size, tuple(round(s, 4) for s in self.scale), tuple(round(r, 4) for r in self.ratio))
+
+
+BRIGHTNESS, CONTRAST, SATURATION = "brightness", "contrast", "saturation"   # the ops of a colour decision
+
+
+class ColorJitter(object):
+    """torchvision.transforms.ColorJitter without hue (the reference passes none).  get_params draws the brightness, contrast and
+    saturation factors with random.uniform(1 - x, 1 + x) (lower end clipped at 0; x = 0: the op is left out and nothing is drawn),
+    then random.shuffle orders them -> ((op, factor), ...) in the order applied."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        if hue:
+            raise NotImplementedError("ColorJitter(hue=%r): atomnas_image_color has no hue op" % (hue,))
+        self.ranges = []
+        for name, v in ((BRIGHTNESS, brightness), (CONTRAST, contrast), (SATURATION, saturation)):
+            if isinstance(v, (tuple, list)):
+                lo, hi = float(v[0]), float(v[1])
+            else:
+                if v < 0:
+                    raise ValueError("If {} is a single number, it must be non negative.".format(name))
+                lo, hi = max(1 - v, 0), 1 + v
+            if not 0 <= lo <= hi:
+                raise ValueError("{} values should be between (0, inf)".format(name))
+            if not lo == hi == 1:
+                self.ranges.append((name, lo, hi))
+
+    def get_params(self):
+        ops = [(name, random.uniform(lo, hi)) for name, lo, hi in self.ranges]
+        random.shuffle(ops)
+        return tuple(ops)
+
+    def __call__(self, img=None):
+        return self.get_params()
+
+    def __repr__(self):
+        return self.__class__.__name__ + '({})'.format(', '.join('{}=({}, {})'.format(*r) for r in self.ranges))
+
+
+IMAGENET_PCA = {'eigval': np.asarray([0.2175, 0.0188, 0.0045]),                    # utils/transforms.py:9-18
+                'eigvec': np.asarray([[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]])}
+
+
+class Lighting(object):
+    """AlexNet-style PCA noise (utils/transforms.py:21-51): the increment added to (R, G, B) in float64.  Draws np.random.randn(3) from
+    numpy's global generator, as the reference does; alphastd == 0 draws nothing."""
+
+    def __init__(self, alphastd, eigval=IMAGENET_PCA['eigval'], eigvec=IMAGENET_PCA['eigvec']):
+        self.alphastd = alphastd
+        assert eigval.shape == (3,)
+        assert eigvec.shape == (3, 3)
+        self.eigval, self.eigvec = eigval, eigvec
+
+    def get_inc(self):
+        if self.alphastd == 0.:
+            return None
+        rnd = (np.random.randn(3) * self.alphastd).astype('float32')
+        v = (rnd * self.eigval).reshape((3, 1))
+        inc = np.dot(self.eigvec, v).reshape((3,))
+        return tuple(float(x) for x in inc)
+
+    def __call__(self, img=None):
+        return self.get_inc()
+
+    def __repr__(self):
+        return self.__class__.__name__ + '()'
+
+
+class Resize(object):
+    """torchvision.transforms.Resize(int): the shorter side becomes `size`, the other int(size * long / short) -> (oh, ow)"""
+
+    def __init__(self, size, interpolation=None):
+        if not isinstance(size, int):
+            raise NotImplementedError("Resize takes the length of the shorter side (an int) here")
+        if interpolation is not None and _interp_name(interpolation) not in ("bilinear", "bicubic"):
+            raise NotImplementedError("atomnas_image_resize_window resizes with PIL's BILINEAR or BICUBIC filter only (got %r)" % (interpolation,))
+        self.size = size
+        self.filter = _interp_name(interpolation) if interpolation is not None else "bilinear"
+
+    def get_size(self, img):
+        w, h = _size_of(img)
+        ow, oh = (self.size, int(self.size * h / w)) if w <= h else (int(self.size * w / h), self.size)
+        return oh, ow
+
+    __call__ = get_size
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(size={0})'.format(self.size)
+
+
+class CenterCrop(object):
+    """torchvision.transforms.CenterCrop's box (top, left, size, size) inside a (width, height) image"""
+
+    def __init__(self, size):
+        self.size = int(size)
+
+    def get_box(self, img):
+        width, height = _size_of(img)
+        return center_crop_box(width, height, self.size, self.size)
+
+    __call__ = get_box
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(size={0})'.format(self.size)
+
+
+# What a sample carries beyond (box, flip).  ops: ((op, factor), ...) in the order applied, or None;  inc: Lighting's (r, g, b)
+# increment, or None;  resize: (oh, ow) -- the WHOLE image is resized to that and `box` is a window of the resized image -- or None
+# (box is a crop of the decoded image, resized to the output size).
+Aug = collections.namedtuple("Aug", ["ops", "inc", "resize"])
+Aug.__new__.__defaults__ = (None, None, None)
+
+EVAL_RESIZE = 256                                                              # utils/dataflow.py:126
+
+
+def color_transforms(image_size=224, crop_scale=0.08, jitter=0.4, lighting=0.1):
+    """the deciders of data_transforms('imagenet1k_mobile' | 'imagenet1k_inception' | ...) (utils/dataflow.py:115-131):
+    (train = (crop, jitter, lighting, flip), val = (resize, centre crop))"""
+    train = (RandomResizedCrop(image_size, scale=(crop_scale, 1.0)), ColorJitter(brightness=jitter, contrast=jitter, saturation=jitter),
+             Lighting(lighting), RandomHorizontalFlip())
+    val = (Resize(EVAL_RESIZE), CenterCrop(image_size))
+    return train, val
 
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # utils/dataflow.py:131-132

@@ -303,6 +303,40 @@ int atomnas_image_preprocess_large(const void* pool, const void* desc, const int
                                    const float* std3, void* out, int out_mode, int filter, void* workspace, long workspace_bytes,
                                    void* stream);
 
+/* ---- the rest of the reference's named transforms ('imagenet1k_mobile', 'imagenet1k_inception'; utils/dataflow.py:92-131).  Added
+ *      without an ABI version change (backwards compatible), like atomnas_image_preprocess_large.  What an image needs beyond
+ *      atomnas_img_desc travels in a second per-image table, a device array of N atomnas_img_aug in batch order. */
+typedef struct atomnas_img_aug {
+  int oh, ow;               /* window mode: the size the WHOLE image is resized to (both > 0) */
+  int top, left;            /* window mode: corner of the S x S output window inside that resized image */
+  int op[3];                /* colour pass, in the order applied: 0 none, 1 brightness, 2 contrast (AT MOST ONE per image), 3 saturation */
+  int pad_;
+  float factor[3];          /* blend factor of each op */
+  float pad2_;
+  double inc[3];            /* Lighting: added to R, G, B in float64, clipped to [0, 255], truncated (all 0: none) */
+} atomnas_img_aug;          /* 72 bytes */
+/* Window mode (transforms.Resize + CenterCrop): output pixel (y, x) of image n is pixel (top + y, left + x) of PIL's
+ * resize((ow, oh), filter) of the whole H x W image -- taps clamped to the image, horizontal pass rounded to uint8 first -- then flip,
+ * ToTensor, Normalize as atomnas_image_preprocess.  The crop box of desc is not read.  This launch handles H <= 9 oh and W <= 9 ow (the
+ * tap budget); images beyond go through atomnas_image_resize_window_large afterwards: the same two-pass form and arguments as
+ * atomnas_image_preprocess_large, with max_rows >= the HEIGHT of every selected image (all its rows take the horizontal pass). */
+int atomnas_image_resize_window(const void* pool, const void* desc, const void* aug, int N, int S, const float* mean3, const float* std3,
+                                void* out, int out_mode, int filter, void* stream);
+int atomnas_image_resize_window_large(const void* pool, const void* desc, const void* aug, const int* sel, int M, int max_rows, int S,
+                                      const float* mean3, const float* std3, void* out, int out_mode, int filter, void* workspace,
+                                      long workspace_bytes, void* stream);
+/* Colour pass: transforms.ColorJitter(brightness, contrast, saturation) in the per-image order op[0..2], then Lighting, on
+ * src = uint8 [N][S][S][3] (out_mode 2 of the resize entry points: resized and flipped), then ToTensor / Normalize into `out` in
+ * out_mode 0 / 1 / 2 as above (2: the uint8 image after the colour ops).  PIL's ImageEnhance arithmetic, byte for byte:
+ *   L(p) = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;  blend(d, p, f) = (uint8) clamp(d + f * (p - d), 0, 255) in fp32, product and
+ *   sum each rounded;  brightness d = 0;  contrast d = int(mean of L over the image as it is when the op runs + 0.5);  saturation
+ *   d = L(p);  every op reads the uint8 image the previous one wrote.
+ * means: device scratch of N ints.  form 0: the library's choice; 1: two launches (a per-image reduction that recomputes the ops in
+ * front of the contrast, then the per-pixel chain); 2: one launch, one workgroup per image with the image in LDS (even S,
+ * S * S * 3 <= 163,584 bytes).  Integer sums only: bit-reproducible. */
+int atomnas_image_color(const void* src, const void* aug, int N, int S, const float* mean3, const float* std3, void* out, int out_mode,
+                        void* means, int form, void* stream);
+
 /* ---- deferred fixed-order reductions (ABI 5).  The weight-gradient entry points (atomnas_pw_gemm_tn, atomnas_dwconv_bwd,
  *   atomnas_expand_bwd, atomnas_project_bwd) write per-workgroup partials to their workspace and sum them in a fixed order with one
  *   small launch each: ~110 launches of a few microseconds per supernet step, every one a ~5 us node of the step's hipGraph.
