@@ -209,28 +209,6 @@ static inline int resident_per_cu(KernelT kern, int threads, size_t lds) {
 int reduce_parts(const float* part, long part_stride, int parts, long n, float* out, int inner, long s_outer, long s_inner,
                  hipStream_t st);
 
-// dwconv_cw.hip: the stride-1 / slab-major instances of the depthwise entry points.  Return -1 when the case is not theirs
-// (the caller goes on with the tile kernels of dwconv.hip), otherwise the launch status.
-int dwconv_cw_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                  float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st);
-int dwconv_cw_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                  const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                  float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, int k, int stride,
-                  int dtype, hipStream_t st);
-
-// dwconv_mm.hip: the bf16 instances of the depthwise forward with the tap arithmetic on the matrix cores (same contract: -1 = not mine)
-int dwconv_mm_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                  float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st);
-int dwconv_mm_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                  const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                  float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, int k, int stride,
-                  int dtype, hipStream_t st);
-int dwconv_mm_supported(int N, int H, int W, int C, int k, int dir);
-// dwconv_mm2.hip: the stride-2 forward on the matrix cores
-int dwconv_mm2_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                   float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st);
-int dwconv_mm2_supported(int N, int H, int W, int C, int k);
-
 // End of one stage of an LDS-DMA ring (all of the stage's global_load_lds copies of this wave have been issued).  An assembler
 // comment, no code: tools/check_asm_waits.py models the ring as a queue of stages and checks every counted `s_waitcnt vmcnt(N)`
 // against the number of copies issued AFTER the end of the stage that wait is for.

@@ -16,9 +16,8 @@
 // 16-byte global loads; the k*k taps then slide over LDS rows held in registers (ds_read_b64 of a channel pair, packed
 // fp32 FMAs), so each element costs one HBM read, one transform and k*k FMAs instead of k reloads and k transforms.
 // LDS rows are padded so that the two tile rows a 32-lane LDS group touches fall into different bank halves.
-#include "common.h"
+#include "dwconv_host.h"
 #include <unordered_map>
-#include <cstdlib>
 #ifndef DW_EXP
 #define DW_EXP 0  // experiment switch for tools/dwbench.py: fwd: 1 no stores, 2 no compute, 3 no LDS commit; bwd: 4 no global flush, 5 no compute, 6 no h stores, 7 no x loads, 8 no dY loads, 9 no yraw loads, 10 no FMA loop, 11 no global memory traffic
 #endif
@@ -834,23 +833,19 @@ static void pick_tiles(DwGeom& g, int rows, int cols, int sw, int cb, int even) 
 // (CUs / 8) * per_cu slots, i.e. whole multiples of 8 workers.  (Round 2 found workers = total_slots / nslabs here, e.g. 17
 // workers x 30 slabs at 14x14x480: XCD 0 got 3 x 30 = 90 workgroups for 64 slots and the kernel ran two rounds; fixing it took
 // the depthwise kernels from 25.4 to 20.7 ms per step.)  In plain order (slab-major layout) any count <= total slots is level.
-static void set_workers(DwGeom& g, int nslabs, int per_cu, int cap, long max_workers, bool xcd_decode) {
+static void set_workers(DwGeom& g, int nslabs, int per_cu, long max_workers, bool xcd_decode) {
   const long ntiles = (long)g.N * g.tiles_y * g.tiles_x;
   if (per_cu < 1) per_cu = 1;
-  if (per_cu > cap) per_cu = cap;
-  constexpr int level_env = 2;   // A/B: 0 round-1 rule, 1 aligned
-  const bool aligned = level_env == 1 || (level_env == 2 && xcd_decode);
-  g.xcd = (level_env == 2 && !xcd_decode) ? 0 : 1;
+  if (per_cu > 8) per_cu = 8;
+  g.xcd = xcd_decode ? 1 : 0;
   const long slots_xcd = (long)(num_cus() / 8) * per_cu;
-  long want = aligned ? (slots_xcd / nslabs) * 8 : ((long)num_cus() * per_cu) / nslabs;
+  long want = xcd_decode ? (slots_xcd / nslabs) * 8 : ((long)num_cus() * per_cu) / nslabs;
   if (want < 8) want = ((long)num_cus() * per_cu) / nslabs;   // more slabs than slots of an XCD: several rounds either way
-  constexpr int share = 1;   // experiment: one of `share` concurrent launches
-  if (share > 1) want = want / share > 0 ? want / share : 1;
-  static const long max_env = getenv("ATOMNAS_DW_MAX_WORKERS") ? atol(getenv("ATOMNAS_DW_MAX_WORKERS")) : 0;   // tests: force long tile walks
+  const long max_env = dw_env().max_workers;
   if (max_env > 0 && want > max_env) want = max_env;
   if (max_workers > 0 && want > max_workers) want = max_workers;   // every worker owns one partial row (statistics, weight gradient)
   if (want > ntiles) want = ntiles;
-  if (aligned && want > 8) want = want / 8 * 8;
+  if (xcd_decode && want > 8) want = want / 8 * 8;
   if (want < 1) want = 1;
   g.nworkers = (int)want;
   g.nslabs = nslabs;
@@ -861,31 +856,30 @@ static inline unsigned dw_grid(const DwGeom& g) {
 }
 
 template <typename T, int K, int S>
-static int launch_fwd(const void* x, int ldx, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y,
-                      int ldy, long yss, float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, hipStream_t st) {
+static int tile_launch_fwd(const DwFwdArgs& a) {
   constexpr int P = (K - 1) / 2;
+  const int H = a.s.H, W = a.s.W, C = a.s.C;
   DwGeom g;
-  g.N = N; g.H = H; g.W = W; g.C = C;
+  g.N = a.s.N; g.H = H; g.W = W; g.C = C;
   g.Ho = (H + 2 * P - K) / S + 1; g.Wo = (W + 2 * P - K) / S + 1;
   const int cpad = (C + 7) / 8 * 8;
   // 14x14 output tiles of 16 channels (several workgroups per CU); small maps take the whole image and 64 channels
   const int sw = 7;
-  constexpr int cb_env = 0;
   // default 16; deviations measured in situ on the supernet's own shapes (bs 256 step, tools/bringup.py DETAIL=1 +
   // tools/cmpdetail.py, re-done after the XCD-level fix of set_workers): 8-channel slabs for the stride-2 layers with few channels
   // per pixel, 32 for C <= 32
   // r03: for slab-major tensors whole slabs win on every stride-2 shape of the step since the prefetch became branch-free (8-channel
-  // workgroups read half of every 32-byte slab row; tools/dwbench.py fwd, ATOMNAS_DW_FWD_CB=16 vs the rule: 1.55 -> 1.36 ms)
+  // workgroups read half of every 32-byte slab row; tools/dwbench.py fwd, 16 vs the rule: 1.55 -> 1.36 ms)
   int cb_rule = 16;
   // One rule for both storage types (round 5).  Rounds 3-4 kept 8-channel slabs for fp32 because regrouping the statistics partials
   // moved tests/golden/checkpoint_ref.pt's element-wise comparison across a ReLU-mask flip; the fixture's resume batch had a
   // pre-activation ON zero (|pre| / rms 7.8e-9).  The fixture now resumes on a wide-margin batch (tools/make_golden.py: 1.75e-6), so
   // the comparison no longer depends on the summation order.
-  const bool whole_slabs = xss != 0;
+  const bool whole_slabs = a.xss != 0;
   if (S == 2 && C <= 96 && !whole_slabs) cb_rule = 8;
   else if (S == 2 && K >= 5 && H <= 56 && !whole_slabs) cb_rule = 8;
   else if (S == 1 && C <= 32) cb_rule = 32;
-  const int cb = slab_width((g.Wo <= 7 && g.Ho <= 7) ? 64 : (cb_env ? cb_env : cb_rule), cpad);
+  const int cb = slab_width((g.Wo <= 7 && g.Ho <= 7) ? 64 : cb_rule, cpad);
   pick_tiles(g, g.Ho, g.Wo, sw, cb, 0);
   ATOMNAS_REQUIRE(cb <= 32 || (g.TH <= 7 && g.TW <= 7), "dwconv_fwd: internal tile configuration error");
   g.LH = (g.TH - 1) * S + K;
@@ -894,38 +888,32 @@ static int launch_fwd(const void* x, int ldx, long xss, const float* sc, const f
   const int nslabs = (cpad + cb - 1) / cb;
   const size_t lds = ((size_t)g.LH * g.RP + (size_t)K * K * cb + 8 * cb) * sizeof(float) + (DW_FWD_STAGE ? (size_t)g.TH * g.TW * cb * sizeof(T) : 0);
   ATOMNAS_REQUIRE(lds <= max_lds_bytes(), "dwconv_fwd: tile does not fit in LDS (%zu bytes)", lds);
-  constexpr int cap_env = 0;
-  const int cap = cap_env ? cap_env : 8;
-#define FWD_CASE(CBV, TMV)                                                                                                   \
-  {                                                                                                                      \
-    auto kern = (relu == ACT_RELU6) ? k_dwconv_fwd<T, K, S, 7, CBV, TMV, ACT_RELU6>                                    \
-                                    : (relu == ACT_SWISH ? k_dwconv_fwd<T, K, S, 7, CBV, TMV, ACT_SWISH> : k_dwconv_fwd<T, K, S, 7, CBV, TMV, 0>);                                                                           \
-    set_workers(g, nslabs, resident_per_cu(kern, 256, lds), cap, stats ? stat_rows : 0, xss == 0);                                      \
-    dim3 grid(dw_grid(g));                                                                                      \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const T*)x, ldx, xss, sc, sh, relu, w, ldw, (T*)y, ldy, yss, stats, stat_ld, stat_rows, g); \
-  }
+  auto launch = [&](auto cbc, auto tmc) {
+    dw_for_act<false>(a.relu, false, [&](auto am) {
+      auto kern = k_dwconv_fwd<T, K, S, 7, decltype(cbc)::value, decltype(tmc)::value, decltype(am)::value>;
+      set_workers(g, nslabs, resident_per_cu(kern, 256, lds), a.stats ? a.stat_rows : 0, a.xss == 0);
+      hipLaunchKernelGGL(kern, dim3(dw_grid(g)), dim3(256), lds, a.st, (const T*)a.x, a.ldx, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw, (T*)a.y,
+                         a.ldy, a.yss, a.stats, a.stat_ld, a.stat_rows, g);
+    });
+  };
   const bool small = g.TH <= 7 && g.TW <= 7;
-  if (cb == 8) { if (small) FWD_CASE(8, 7) else FWD_CASE(8, 14) }
-  else if (cb == 16) { if (small) FWD_CASE(16, 7) else FWD_CASE(16, 14) }
-  else if (cb == 32) { if (small) FWD_CASE(32, 7) else FWD_CASE(32, 14) }
-  else FWD_CASE(64, 7)
-#undef FWD_CASE
+  if (cb == 8) { if (small) launch(IC<8>{}, IC<7>{}); else launch(IC<8>{}, IC<14>{}); }
+  else if (cb == 16) { if (small) launch(IC<16>{}, IC<7>{}); else launch(IC<16>{}, IC<14>{}); }
+  else if (cb == 32) { if (small) launch(IC<32>{}, IC<7>{}); else launch(IC<32>{}, IC<14>{}); }
+  else launch(IC<64>{}, IC<7>{});
   return check_launch("dwconv_fwd");
 }
 
-template <typename T, int K, int S, int SW>
-static int launch_bwd_sw(const void* gup, int ldg, long gss, const void* yraw, int ldyr, long yrss, const float* c1, const float* c2,
-                         const float* c3, const void* x, int ldx, long xss, const float* sc, const float* sh, int relu, const float* w,
-                         int ldw, void* h, int ldh, long hss, float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C,
-                         hipStream_t st) {
-  constexpr int P = (K - 1) / 2;
+template <typename T, int K, int S>
+static int tile_launch_bwd(const DwBwdArgs& a) {
+  constexpr int P = (K - 1) / 2, SW = (S == 2) ? 14 : 7;
+  const int H = a.s.H, W = a.s.W, C = a.s.C;
   DwGeom g;
-  g.N = N; g.H = H; g.W = W; g.C = C;
+  g.N = a.s.N; g.H = H; g.W = W; g.C = C;
   g.Ho = (H + 2 * P - K) / S + 1; g.Wo = (W + 2 * P - K) / S + 1;
   const int cpad = (C + 7) / 8 * 8;
   // measured (tools/dwbench.py): 32-channel slabs win for stride 2 and for 7x7 maps with k <= 5, 16-channel slabs elsewhere
   // (k = 7 with 32 channels spills its 98 weight-gradient accumulators)
-  constexpr int cb_env = 0;
   // in-situ deviations (same sweep as the forward, re-done after the XCD-level fix of set_workers): k = 5 at 28x28 and 14x14
   // prefers 32
   int cb_rule = (S == 2 || (H <= 7 && W <= 7 && K <= 5)) ? 32 : 16;
@@ -935,8 +923,7 @@ static int launch_bwd_sw(const void* gup, int ldg, long gss, const void* yraw, i
   // items; 16 channels: 56).  The prefetch registers are sized for the 7-pixel tile there (template parameter TM).
   const bool small = (S == 1 && H <= 7 && W <= 7);
   if (small) cb_rule = (K == 7) ? DW_SMALL_CB7 : 64;
-  if (S == 1 && SW == 14) cb_rule = 32;   // one 14-pixel strip per row: 16 channel pairs x 14 rows = 224 work items
-  const int cb = slab_width((S == 1 && SW == 14) ? cb_rule : (cb_env ? cb_env : cb_rule), cpad);
+  const int cb = slab_width(cb_rule, cpad);
   pick_tiles(g, H, W, SW, cb, S == 2);
   // output window of an input tile: rows ceil((hi0+P-K+1)/S) .. floor((hi0+TH-1+P)/S)
   g.LH = fdiv(g.TH - 1 + P, S) - cdiv(P - (K - 1), S) + 1;
@@ -950,50 +937,23 @@ static int launch_bwd_sw(const void* gup, int ldg, long gss, const void* yraw, i
   const size_t lds = ((size_t)g.LH * g.RP + (size_t)K * K * cb + (size_t)cb * (K * K + 2) + 3 * (size_t)cb) * sizeof(float) +
                      (size_t)2 * tm * tm * cb * sizeof(T) + ((DW_DMA && sizeof(T) == 2) ? (size_t)2 * pf * 256 * 16 : 0);
   ATOMNAS_REQUIRE(lds <= max_lds_bytes(), "dwconv_bwd: tile does not fit in LDS (%zu bytes)", lds);
-  constexpr int cap_env2 = 0;
-  const int cap = cap_env2 ? cap_env2 : 8;
-#define BWD_CASE(CBV, TMV)                                                                                                \
-  {                                                                                                                       \
-    auto kern = (relu == ACT_RELU6) ? k_dwconv_bwd<T, K, S, SW, CBV, TMV, ACT_RELU6>                                   \
-                                    : (relu == ACT_SWISH ? k_dwconv_bwd<T, K, S, SW, CBV, TMV, ACT_SWISH> : k_dwconv_bwd<T, K, S, SW, CBV, TMV, 0>);                                                                           \
-    set_workers(g, nslabs, resident_per_cu(kern, 256, lds), cap, (stats || dw) ? part_rows : 0, xss == 0 || gss == 0);                               \
-    dim3 grid(dw_grid(g));                                                                                       \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const T*)gup, ldg, gss, (const T*)yraw, ldyr, yrss, c1, c2, c3, (const T*)x, \
-                       ldx, xss, sc, sh, relu, w, ldw, (T*)h, ldh, hss, dw ? dw_ws : nullptr, stats, stat_ld, part_rows, g); \
-  }
-  if constexpr (S == 1 && SW == 14) {
-    ATOMNAS_REQUIRE(cb == 32 && !small, "dwconv_bwd: wide strips need 32-channel slabs and tiles of 14 pixels");
-    BWD_CASE(32, 14)
-  } else if constexpr (S == 1) {
-    if (small) {
-      if (cb == 8) BWD_CASE(8, 7) else if (cb == 16) BWD_CASE(16, 7) else if (cb == 32) BWD_CASE(32, 7) else BWD_CASE(64, 7)
-    } else {
-      if (cb == 8) BWD_CASE(8, 14) else if (cb == 16) BWD_CASE(16, 14) else BWD_CASE(32, 14)
+  auto launch = [&](auto cbc, auto tmc) {
+    dw_for_act<false>(a.relu, false, [&](auto am) {
+      auto kern = k_dwconv_bwd<T, K, S, SW, decltype(cbc)::value, decltype(tmc)::value, decltype(am)::value>;
+      set_workers(g, nslabs, resident_per_cu(kern, 256, lds), (a.stats || a.dw) ? a.part_rows : 0, a.xss == 0 || a.gss == 0);
+      hipLaunchKernelGGL(kern, dim3(dw_grid(g)), dim3(256), lds, a.st, (const T*)a.gup, a.ldg, a.gss, (const T*)a.yraw, a.ldyr, a.yrss, a.c1,
+                         a.c2, a.c3, (const T*)a.x, a.ldx, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw, (T*)a.h, a.ldh, a.hss,
+                         a.dw ? a.dw_ws : nullptr, a.stats, a.stat_ld, a.part_rows, g);
+    });
+  };
+  if (small) {
+    if constexpr (S == 1) {   // (small implies stride 1: the 7-pixel tile instances exist for it only)
+      if (cb == 8) launch(IC<8>{}, IC<7>{}); else if (cb == 16) launch(IC<16>{}, IC<7>{}); else if (cb == 32) launch(IC<32>{}, IC<7>{}); else launch(IC<64>{}, IC<7>{});
     }
   } else {
-    if (cb == 8) BWD_CASE(8, 14) else if (cb == 16) BWD_CASE(16, 14) else BWD_CASE(32, 14)
+    if (cb == 8) launch(IC<8>{}, IC<14>{}); else if (cb == 16) launch(IC<16>{}, IC<14>{}); else launch(IC<32>{}, IC<14>{});
   }
-#undef BWD_CASE
-  if (int rc = check_launch("dwconv_bwd")) return rc;
-  // dw[c][t] += sum over workers of the partials, in worker order
-  if (dw) return reduce_parts(dw_ws, (long)C * K * K, g.nworkers, (long)C * K * K, dw, C * K * K, 0, 1, st);
-  return 0;
-}
-
-template <typename T, int K, int S>
-static int launch_bwd(const void* gup, int ldg, long gss, const void* yraw, int ldyr, long yrss, const float* c1, const float* c2,
-                      const float* c3, const void* x, int ldx, long xss, const float* sc, const float* sh, int relu, const float* w,
-                      int ldw, void* h, int ldh, long hss, float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C,
-                      hipStream_t st) {
-  // experiment (ATOMNAS_DW_BWD_SW14=k-mask, bit 0: k = 3, bit 1: k = 5): 14-pixel strips for stride 1 -- 27 % fewer LDS reads per FMA
-  if constexpr (sizeof(T) == 2 && S == 1 && K <= 5) {
-    constexpr int wide_env = 0;
-    if (((wide_env >> (K == 3 ? 0 : 1)) & 1) && H > 7 && W >= 14 && C >= 32)
-      return launch_bwd_sw<T, K, S, 14>(gup, ldg, gss, yraw, ldyr, yrss, c1, c2, c3, x, ldx, xss, sc, sh, relu, w, ldw, h, ldh, hss, dw, stats,
-                                         stat_ld, part_rows, dw_ws, N, H, W, C, st);
-  }
-  return launch_bwd_sw<T, K, S, (S == 2) ? 14 : 7>(gup, ldg, gss, yraw, ldyr, yrss, c1, c2, c3, x, ldx, xss, sc, sh, relu, w, ldw, h, ldh, hss, dw,
-                                                    stats, stat_ld, part_rows, dw_ws, N, H, W, C, st);
+  return dw_finish_bwd("dwconv_bwd", a, g.nworkers);
 }
 
 #if DW_TIMING
@@ -1008,24 +968,27 @@ extern "C" int atomnas_debug_dw_timing(unsigned long long* out8, int reset) {
 namespace atomnas {
 #endif
 
-#define DW_DISPATCH(FN, ...)                                                                   \
-  do {                                                                                         \
-    if (dtype == DT_F32) {                                                                     \
-      if (k == 3 && stride == 1) return FN<float, 3, 1>(__VA_ARGS__);                          \
-      if (k == 3 && stride == 2) return FN<float, 3, 2>(__VA_ARGS__);                          \
-      if (k == 5 && stride == 1) return FN<float, 5, 1>(__VA_ARGS__);                          \
-      if (k == 5 && stride == 2) return FN<float, 5, 2>(__VA_ARGS__);                          \
-      if (k == 7 && stride == 1) return FN<float, 7, 1>(__VA_ARGS__);                          \
-      if (k == 7 && stride == 2) return FN<float, 7, 2>(__VA_ARGS__);                          \
-    } else {                                                                                   \
-      if (k == 3 && stride == 1) return FN<bf16_t, 3, 1>(__VA_ARGS__);                         \
-      if (k == 3 && stride == 2) return FN<bf16_t, 3, 2>(__VA_ARGS__);                         \
-      if (k == 5 && stride == 1) return FN<bf16_t, 5, 1>(__VA_ARGS__);                         \
-      if (k == 5 && stride == 2) return FN<bf16_t, 5, 2>(__VA_ARGS__);                         \
-      if (k == 7 && stride == 1) return FN<bf16_t, 7, 1>(__VA_ARGS__);                         \
-      if (k == 7 && stride == 2) return FN<bf16_t, 7, 2>(__VA_ARGS__);                         \
-    }                                                                                          \
-  } while (0)
+// THE order of the kernel families; the first plan that accepts runs.  (Each plan declines what is not its own: mm2 takes the stride-2
+// forward only, mm stride 1 only, cw stride 1 and the stride-2 backward.)  The tile kernels of this file take everything else.
+DwFamily dw_pick(const DwShape& s, int dir, DwPlan& p) {
+  if (mm2_plan(s, dir, p)) return DW_MM2;
+  if (mm_plan(s, dir, p)) return DW_MM;
+  if (cw_plan(s, dir, p)) return DW_CW;
+  return DW_TILE;
+}
+
+// the tile kernels: every k, stride, storage type and layout
+template <typename F> static int tile_dispatch(const DwShape& s, F&& f) {
+  return dw_for_type(s.dtype, [&](auto tt) {
+    return dw_for_k(s.k, [&](auto kc) { return s.stride == 1 ? f(tt, kc, IC<1>{}) : f(tt, kc, IC<2>{}); });
+  });
+}
+
+// the shape of a *_supported query (slab-major operands, padded tap table); false for what the entry points reject outright
+static bool dw_query(DwShape& s, int N, int H, int W, int C, int k, int stride, int dtype) {
+  s = DwShape{N, H, W, C, k, stride, dtype, true};
+  return (k == 3 || k == 5 || k == 7) && (stride == 1 || stride == 2) && (dtype == DT_F32 || dtype == DT_BF16) && N > 0 && H > 0 && W > 0 && C > 0;
+}
 
 }  // namespace atomnas
 
@@ -1051,18 +1014,19 @@ extern "C" int atomnas_dwconv_fwd(const void* x, int ldx, long x_ss, const float
   }
   ATOMNAS_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_fwd: scale/shift must come together");
   ATOMNAS_REQUIRE(!stats || (stat_ld >= C && stat_rows > 0), "dwconv_fwd: statistics pitch %d < C=%d or stat_rows=%d", stat_ld, C, stat_rows);
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {
-    int rc = dwconv_mm_fwd(x, x_ss, in_scale, in_shift, in_relu, w, ldw, y, y_ss, stats, stat_ld, stat_rows, N, H, W, C, k, dtype, st);
-    if (rc >= 0) return rc;
-    rc = dwconv_cw_fwd(x, x_ss, in_scale, in_shift, in_relu, w, ldw, y, y_ss, stats, stat_ld, stat_rows, N, H, W, C, k, dtype, st);
-    if (rc >= 0) return rc;
-  } else {
-    const int rc = dwconv_mm2_fwd(x, x_ss, in_scale, in_shift, in_relu, w, ldw, y, y_ss, stats, stat_ld, stat_rows, N, H, W, C, k, dtype, st);
-    if (rc >= 0) return rc;
+  const bool slab = x_ss != 0 && y_ss != 0 && ldw >= cpad;
+  const DwFwdArgs a = {{N, H, W, C, k, stride, dtype, slab}, x, ldx, x_ss, in_scale, in_shift, in_relu, w, ldw, y, ldy, y_ss,
+                       stats, stat_ld, stat_rows, (hipStream_t)stream};
+  DwPlan p;
+  switch (dw_pick(a.s, 0, p)) {
+    case DW_MM2: return mm2_launch_fwd(p, a);
+    case DW_MM: return mm_launch_fwd(p, a);
+    case DW_CW: return cw_launch_fwd(p, a);
+    case DW_TILE: break;
   }
-  DW_DISPATCH(launch_fwd, x, ldx, x_ss, in_scale, in_shift, in_relu, w, ldw, y, ldy, y_ss, stats, stat_ld, stat_rows, N, H, W, C, st);
-  return 1;
+  return tile_dispatch(a.s, [&](auto tt, auto kc, auto sc) {
+    return tile_launch_fwd<typename decltype(tt)::type, decltype(kc)::value, decltype(sc)::value>(a);
+  });
 }
 
 extern "C" int atomnas_dwconv_bwd(const void* g, int ldg, long g_ss, const void* yraw, int ldyr, long yraw_ss, const float* c1,
@@ -1084,16 +1048,36 @@ extern "C" int atomnas_dwconv_bwd(const void* g, int ldg, long g_ss, const void*
   ATOMNAS_REQUIRE(!stats || stat_ld >= C, "dwconv_bwd: statistics pitch %d < C=%d", stat_ld, C);
   ATOMNAS_REQUIRE(!(stats || dw) || part_rows > 0, "dwconv_bwd: part_rows must be positive");
   ATOMNAS_REQUIRE(!dw || dw_ws, "dwconv_bwd: the weight gradient needs the partial workspace dw_ws [part_rows][C][k*k]");
-  hipStream_t st = (hipStream_t)stream;
-  {
-    int rc = dwconv_mm_bwd(g, g_ss, yraw, yraw_ss, c1, c2, c3, x, x_ss, in_scale, in_shift, in_relu, w, ldw, h, h_ss, dw, stats, stat_ld,
-                           part_rows, dw_ws, N, H, W, C, k, stride, dtype, st);
-    if (rc >= 0) return rc;
-    rc = dwconv_cw_bwd(g, g_ss, yraw, yraw_ss, c1, c2, c3, x, x_ss, in_scale, in_shift, in_relu, w, ldw, h, h_ss, dw, stats, stat_ld,
-                       part_rows, dw_ws, N, H, W, C, k, stride, dtype, st);
-    if (rc >= 0) return rc;
+  const bool slab = g_ss != 0 && x_ss != 0 && h_ss != 0 && (!yraw || yraw_ss != 0) && ldw >= cpad;
+  const DwBwdArgs a = {{N, H, W, C, k, stride, dtype, slab}, g, ldg, g_ss, yraw, ldyr, yraw_ss, c1, c2, c3, x, ldx, x_ss, in_scale, in_shift,
+                       in_relu, w, ldw, h, ldh, h_ss, dw, stats, stat_ld, part_rows, dw_ws, (hipStream_t)stream};
+  DwPlan p;
+  switch (dw_pick(a.s, 1, p)) {
+    case DW_MM: return mm_launch_bwd(p, a);
+    case DW_CW: return cw_launch_bwd(p, a);
+    default: break;   // (no backward in the mm2 family)
   }
-  DW_DISPATCH(launch_bwd, g, ldg, g_ss, yraw, ldyr, yraw_ss, c1, c2, c3, x, ldx, x_ss, in_scale, in_shift, in_relu, w, ldw, h, ldh,
-              h_ss, dw, stats, stat_ld, part_rows, dw_ws, N, H, W, C, st);
-  return 1;
+  return tile_dispatch(a.s, [&](auto tt, auto kc, auto sc) {
+    return tile_launch_bwd<typename decltype(tt)::type, decltype(kc)::value, decltype(sc)::value>(a);
+  });
+}
+
+// 1 when atomnas_dwconv_fwd (dir = 0) / atomnas_dwconv_bwd (dir = 1) run the shape on the matrix cores (bf16 slab-major tensors:
+// dwconv_mm.hip, or the stride-2 forward of dwconv_mm2.hip).  Tests build the oracle's storage model from it
+// (oracle/atomnas_oracle.py bf16_storage_mm).
+extern "C" int atomnas_dwconv_mm_supported(int N, int H, int W, int C, int k, int stride, int dtype, int dir) {
+  DwShape s;
+  DwPlan p;
+  if (!dw_query(s, N, H, W, C, k, stride, dtype)) return 0;
+  const DwFamily f = dw_pick(s, dir != 0, p);
+  return f == DW_MM || f == DW_MM2;
+}
+
+// 1 when the channel-pair-per-wave kernels of dwconv_cw.hip ACCEPT the shape (slab-major tensors) -- whether or not the matrix-core
+// kernels, which come first in dw_pick, take it from them: the answer to "would cw_plan run this", not to "does it run".  Tests and
+// launch-geometry tools only.
+extern "C" int atomnas_dwconv_cw_supported(int N, int H, int W, int C, int k, int stride, int dtype, int dir) {
+  DwShape s;
+  DwPlan p;
+  return dw_query(s, N, H, W, C, k, stride, dtype) && cw_plan(s, dir != 0, p);
 }

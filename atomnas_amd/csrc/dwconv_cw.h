@@ -1,9 +1,9 @@
-// Shared pieces of the "one channel pair per wave" depthwise kernels (gfx950): tile geometry, storage-type plumbing, staging-slot
-// decode, workgroup -> (slab, worker, half) mapping, launch sizing.  Included by dwconv_cw.hip (packed-FMA tap rows), dwconv_mm.hip
-// (tap rows on the matrix cores) and the round-4 experiment csrc/experimental/xdw_cw_bwd.hip.  See dwconv_cw.hip for the design.
+// Shared pieces of the depthwise sources (gfx950).  Device side: tile geometry, storage-type plumbing, staging-slot decode and the
+// workgroup -> (slab, worker, half) mapping of the "one channel pair per wave" kernels (dwconv_cw.hip: packed-FMA tap rows, see there
+// for the design; dwconv_mm.hip / dwconv_mm2.hip: tap rows on the matrix cores; csrc/experimental/xdw_cw_bwd.hip).  The host side
+// (argument structs, switches, plans, geometry functions) is dwconv_host.h.
 #pragma once
 #include "common.h"
-#include <cstdlib>
 
 #ifndef CW_TIMING
 #define CW_TIMING 0   // experiment builds (tools/variant.sh): s_memtime accounting of the phases of a tile in the backward kernel
@@ -37,6 +37,17 @@ struct CwGeom {
   // stride-2 kernels (k_dwb_cw2 / k_dwf_cw2): the lanes live on the dY / output grid (Ho x Wo), the window holds that grid
   int Ho, Wo, THd;           // output rows / columns, output rows per tile (TH = 2 THd input rows)
   int TPIXD;                 // output pixels per tile
+};
+
+// extra geometry of the matrix-core kernels on top of CwGeom (tiles, workers and the staging slots are dwconv_cw.hip's)
+struct MmGeom {
+  int nrp, ncb, ntl, ngroups;   // row pairs / 8-column blocks per image of the pixel tile, MFMA tiles per pixel tile, groups of 16
+  int nkb, xwp, xplane, steps;  // backward: 8-column blocks of a window row, row pitch / plane elements of the activated-input copies,
+                                // groups of four rows of the pixel tile (weight gradient: nkb MFMAs per group)
+};
+struct Mm2Geom {   // dwconv_mm2.hip
+  int nrp, ncb, ntl, ngroups;   // row pairs / 8-column blocks of the OUTPUT band per image, MFMA tiles per pixel tile, groups of 16
+  int TPIXDp;                   // pitch of the output pixel planes
 };
 
 // storage-type plumbing: `piece` = 8 channels of one pixel (16-byte global accesses), `pair` = one channel pair of one pixel
@@ -191,117 +202,5 @@ __device__ __forceinline__ bool cw_block(const CwGeom& g, int& slab, int& worker
 }
 
 constexpr __host__ __device__ int cw_fdiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-
-// ---------------------------------------------------------------------------------------------------------------- host side
-static bool cw_geometry(CwGeom& g, int N, int H, int W, int C, int K) {
-  if (W % 7 != 0 || W < 7) return false;
-  g.N = N; g.H = H; g.W = W; g.C = C;
-  g.ns = W / 7;
-  if (g.ns > 16) return false;
-  if (H * g.ns <= 64) {   // whole images
-    g.TH = H; g.tiles_y = 1; g.NI = 64 / (H * g.ns); g.ring = 0;
-    if (g.NI > N) g.NI = N;
-  } else {
-    const int cap = 64 / g.ns;
-    const int nty = (H + cap - 1) / cap;
-    g.TH = (H + nty - 1) / nty;
-    g.tiles_y = (H + g.TH - 1) / g.TH;
-    g.NI = 1; g.ring = 1;
-  }
-  g.LH = g.TH + K - 1;
-  // row pitch: the 32 lanes of an LDS group are (rows x strips); their first elements r * LWp + 7 * j must differ mod 32 (8-byte
-  // bank pairs): LWp = ns (mod 2 ns) for ns a power of two does it (7 is invertible mod 32), an odd pitch otherwise
-  const int lw = W + K - 1;
-  const bool pow2 = (g.ns & (g.ns - 1)) == 0;
-  int lwp = lw;
-  if (pow2) { while (lwp % (2 * g.ns) != g.ns) ++lwp; } else if (lwp % 2 == 0) ++lwp;
-  g.LWp = lwp;
-  g.RH = g.LH;
-  int plane = g.NI * g.RH * g.LWp;
-  if (plane < 512) plane = 512;      // the weight-gradient flush transposes 64 x 15 + 56 floats through a wave's own plane
-  while (plane % 4 != 2) ++plane;     // staging writes of the two channel groups land in different bank halves
-  g.plane = plane;
-  g.TPIX = g.NI * g.TH * W;
-  int tp = g.TPIX;
-  while (tp % 8 != 4) ++tp;
-  g.TPIXp = tp;
-  g.ntiles = ((N + g.NI - 1) / g.NI) * g.tiles_y;
-  g.nslabs = (C + 15) / 16;
-  return true;
-}
-
-// stride 2: the lane grid is the output grid; K decides the halo rows / columns of the window
-static bool cw2_geometry(CwGeom& g, int N, int H, int W, int C, int K) {
-  if (H % 2 || W % 14 != 0 || W < 14) return false;
-  const int P = (K - 1) / 2;
-  const int RELMIN = cw_fdiv(-P, 2), RELMAX = cw_fdiv(13 + P, 2), CL = -RELMIN, CR = RELMAX - 6;
-  const int HL = P / 2 + cw_fdiv(P - 1, 2) + 1;
-  g.N = N; g.H = H; g.W = W; g.C = C;
-  g.Ho = H / 2; g.Wo = W / 2;
-  g.ns = g.Wo / 7;
-  if (g.ns > 16) return false;
-  if (g.Ho * g.ns <= 64) {   // whole images
-    g.THd = g.Ho; g.tiles_y = 1; g.NI = 64 / (g.Ho * g.ns); g.ring = 0;
-    if (g.NI > N) g.NI = N;
-  } else {
-    const int cap = 64 / g.ns;
-    const int nty = (g.Ho + cap - 1) / cap;
-    g.THd = (g.Ho + nty - 1) / nty;
-    g.tiles_y = (g.Ho + g.THd - 1) / g.THd;
-    g.NI = 1; g.ring = 1;
-  }
-  g.TH = 2 * g.THd;
-  g.LH = g.THd + HL;
-  const int lw = g.Wo + CL + CR;
-  const bool pow2 = (g.ns & (g.ns - 1)) == 0;
-  int lwp = lw;
-  if (pow2) { while (lwp % (2 * g.ns) != g.ns) ++lwp; } else if (lwp % 2 == 0) ++lwp;
-  g.LWp = lwp;
-  g.RH = g.LH;
-  int plane = g.NI * g.RH * g.LWp + 4;   // + slack: a half strip reads a fixed number of operand pairs, up to 2 past its last one
-  if (plane < 512) plane = 512;
-  while (plane % 4 != 2) ++plane;
-  g.plane = plane;
-  g.TPIX = g.NI * g.TH * W;
-  g.TPIXD = g.NI * g.THd * g.Wo;
-  int tp = g.TPIX;
-  while (tp % 8 != 4) ++tp;
-  g.TPIXp = tp;
-  g.ntiles = ((N + g.NI - 1) / g.NI) * g.tiles_y;
-  g.nslabs = (C + 15) / 16;
-  return true;
-}
-
-static void cw_workers(CwGeom& g, int per_cu, int max_rows, int nw) {
-  if (per_cu < 1) per_cu = 1;
-  const int units = g.nslabs * (nw == 4 ? 2 : 1);   // workgroups per worker
-  // experiment switch: this launch is one of `share` concurrent ones (the branches of a block on separate streams): 1 / share of the slots
-  constexpr int share = 1;
-  long want = ((long)num_cus() * per_cu) / units / (share > 1 ? share : 1);
-  static const long max_env = getenv("ATOMNAS_DW_MAX_WORKERS") ? atol(getenv("ATOMNAS_DW_MAX_WORKERS")) : 0;   // tests: long tile walks
-  if (max_env > 0 && want > max_env) want = max_env;
-  if (max_rows > 0 && want > max_rows) want = max_rows;   // every worker owns one partial row
-  if (want > g.ntiles) want = g.ntiles;
-  if (want < 1) want = 1;
-  g.nworkers = (int)want;
-}
-static unsigned cw_grid(const CwGeom& g, int nw) {
-  const unsigned u = (unsigned)g.nworkers * g.nslabs;
-  return nw == 4 ? (u + 7) / 8 * 16 : u;   // half-slab workgroups: 8 (slab, worker) units -> 16 blocks, see cw_block
-}
-
-static int cw_mode() {
-  // bit 0: backward, bit 1: forward (stride 1); bit 2: backward stride 2, bit 3: forward stride 2
-  static const int m = getenv("ATOMNAS_DW_CW") ? atoi(getenv("ATOMNAS_DW_CW")) : 7;
-  return m;
-}
-static int cw_nw() {
-  constexpr int m = 4;   // waves per workgroup: 8 (whole slab) or 4 (half)
-  return m == 8 ? 8 : 4;
-}
-template <typename T> static size_t cw_lds(const CwGeom& g, int nw) {
-  typedef typename Cw<T>::pair_t pair_t;
-  return (size_t)nw * g.plane * sizeof(f32x2) + (size_t)nw * g.TPIXp * sizeof(pair_t) + 48 * sizeof(float);
-}
 
 }  // namespace atomnas

@@ -22,7 +22,7 @@
 // Numerics: identical arithmetic per element to dwconv.hip (fp32 accumulation, one rounding to the storage type); per-channel
 // sums are per-lane partials added in a fixed order (lanes by butterfly, workers by reduce_parts / the BatchNorm finalize), so
 // results are bit-reproducible.  No atomics.
-#include "dwconv_cw.h"
+#include "dwconv_host.h"
 
 namespace atomnas {
 
@@ -860,121 +860,49 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_dwf_cw(const T* __restrict__ x
 }
 
 
-template <typename T, int K>
-static int cw_launch_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                         const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                         float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  if (!cw_geometry(g, N, H, W, C, K)) return -1;
-  const int nw = cw_nw();
-  const size_t lds = cw_lds<T>(g, nw);
-  if (lds > max_lds_bytes()) return -1;
-  // waves per SIMD the instances are compiled for: half-slab workgroups 3 (k = 3: 139 registers) or 2; whole-slab workgroups 2
-  constexpr int WPS4 = K == 3 ? 3 : 2;
-#define CW_BWD(KERN, AMV, NWV, WPSV)                                                                                        \
-  {                                                                                                                         \
-    auto kern = KERN<T, K, AMV, NWV, WPSV, (K == 7)>;                                                                                 \
-    cw_workers(g, resident_per_cu(kern, NWV * 64, lds), (stats || dw) ? part_rows : 0, NWV);                                \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, NWV)), dim3(NWV * 64), lds, st, (const T*)gup, gss, (const T*)yraw, yrss, c1, c2, \
-                       c3, (const T*)x, xss, sc, sh, relu, w, ldw, (T*)h, hss, dw ? dw_ws : nullptr, stats, stat_ld, part_rows, g); \
-  }
-  if (nw == 4) {
-    if (relu == ACT_RELU6) CW_BWD(k_dwb_cw, ACT_RELU6, 4, WPS4) else if (relu == ACT_SWISH) CW_BWD(k_dwb_cw, ACT_SWISH, 4, WPS4) else CW_BWD(k_dwb_cw, 0, 4, WPS4)
-  } else {
-    if (relu == ACT_RELU6) CW_BWD(k_dwb_cw, ACT_RELU6, 8, 2) else if (relu == ACT_SWISH) CW_BWD(k_dwb_cw, ACT_SWISH, 8, 2) else CW_BWD(k_dwb_cw, 0, 8, 2)
-  }
-#undef CW_BWD
-  if (int rc = check_launch("dwconv_bwd(cw)")) return rc;
-  if (dw) return reduce_parts(dw_ws, (long)C * K * K, g.nworkers, (long)C * K * K, dw, C * K * K, 0, 1, st);
-  return 0;
+bool cw_plan(const DwShape& s, int dir, DwPlan& p) {
+  const int mode = dw_env().cw;
+  if (!s.slab) return false;
+  if (dir == 0 ? (s.stride != 1 || !(mode & 2)) : (!(mode & 1) || (s.stride == 2 && !(mode & 4)))) return false;   // stride 2: backward only so far
+  if (!(s.stride == 2 ? cw2_geometry(p.g, s.N, s.H, s.W, s.C, s.k) : cw_geometry(p.g, s.N, s.H, s.W, s.C, s.k))) return false;
+  p.lds = cw_lds(p.g, s.dtype);
+  return p.lds <= max_lds_bytes();
 }
 
-template <typename T, int K>
-static int cw_launch_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                         float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  if (!cw_geometry(g, N, H, W, C, K)) return -1;
-  const int nw = cw_nw();
-  const size_t lds = cw_lds<T>(g, nw);
-  if (lds > max_lds_bytes()) return -1;
-#define CW_FWD(AMV, NWV)                                                                                                    \
-  {                                                                                                                         \
-    auto kern = k_dwf_cw<T, K, AMV, NWV, 4>;                                                                                \
-    cw_workers(g, resident_per_cu(kern, NWV * 64, lds), stats ? stat_rows : 0, NWV);                                        \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, NWV)), dim3(NWV * 64), lds, st, (const T*)x, xss, sc, sh, relu, w, ldw, (T*)y, yss, \
-                       stats, stat_ld, stat_rows, g);                                                                       \
-  }
-  if (nw == 4) {
-    if (relu == ACT_RELU6) CW_FWD(ACT_RELU6, 4) else if (relu == ACT_SWISH) CW_FWD(ACT_SWISH, 4) else CW_FWD(0, 4)
-  } else {
-    if (relu == ACT_RELU6) CW_FWD(ACT_RELU6, 8) else if (relu == ACT_SWISH) CW_FWD(ACT_SWISH, 8) else CW_FWD(0, 8)
-  }
-#undef CW_FWD
+int cw_launch_fwd(const DwPlan& p, const DwFwdArgs& a) {
+  CwGeom g = p.g;
+  dw_for_type(a.s.dtype, [&](auto tt) {
+    dw_for_k(a.s.k, [&](auto kc) {
+      dw_for_act<false>(a.relu, false, [&](auto am) {
+        typedef typename decltype(tt)::type T;
+        auto kern = k_dwf_cw<T, decltype(kc)::value, decltype(am)::value, 4, 4>;
+        cw_workers(g, resident_per_cu(kern, 256, p.lds), a.stats ? a.stat_rows : 0);
+        hipLaunchKernelGGL(kern, dim3(cw_grid(g)), dim3(256), p.lds, a.st, (const T*)a.x, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw, (T*)a.y,
+                           a.yss, a.stats, a.stat_ld, a.stat_rows, g);
+      });
+    });
+  });
   return check_launch("dwconv_fwd(cw)");
 }
 
-template <typename T, int K>
-static int cw2_launch_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                          const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                          float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  if (!cw2_geometry(g, N, H, W, C, K)) return -1;
-  const size_t lds = cw_lds<T>(g, 4);
-  if (lds > max_lds_bytes()) return -1;
-#define CW2_BWD(AMV)                                                                                                        \
-  {                                                                                                                         \
-    auto kern = k_dwb_cw2<T, K, AMV, 4, 2>;                                                                                 \
-    cw_workers(g, resident_per_cu(kern, 256, lds), (stats || dw) ? part_rows : 0, 4);                                       \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, 4)), dim3(256), lds, st, (const T*)gup, gss, (const T*)yraw, yrss, c1, c2,     \
-                       c3, (const T*)x, xss, sc, sh, relu, w, ldw, (T*)h, hss, dw ? dw_ws : nullptr, stats, stat_ld, part_rows, g); \
-  }
-  if (relu == ACT_RELU6) CW2_BWD(ACT_RELU6) else if (relu == ACT_SWISH) CW2_BWD(ACT_SWISH) else CW2_BWD(0)
-#undef CW2_BWD
-  if (int rc = check_launch("dwconv_bwd(cw2)")) return rc;
-  if (dw) return reduce_parts(dw_ws, (long)C * K * K, g.nworkers, (long)C * K * K, dw, C * K * K, 0, 1, st);
-  return 0;
-}
-
-
-// -1: not one of this file's cases (the caller continues with the tile kernels of dwconv.hip); otherwise the launch status
-int dwconv_cw_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                  const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                  float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, int k, int stride,
-                  int dtype, hipStream_t st) {
-  if (!(cw_mode() & 1) || gss == 0 || xss == 0 || hss == 0 || (yraw && yrss == 0) || ldw < ((C + 7) & ~7)) return -1;
-  if (stride == 2) {
-    if (!(cw_mode() & 4)) return -1;
-#define CW_B2(TT, KV) return cw2_launch_bwd<TT, KV>(gup, gss, yraw, yrss, c1, c2, c3, x, xss, sc, sh, relu, w, ldw, h, hss, dw, stats, stat_ld, part_rows, dw_ws, N, H, W, C, st)
-    if (dtype == DT_F32) {
-      if (k == 3) CW_B2(float, 3); if (k == 5) CW_B2(float, 5); if (k == 7) CW_B2(float, 7);
-    } else {
-      if (k == 3) CW_B2(bf16_t, 3); if (k == 5) CW_B2(bf16_t, 5); if (k == 7) CW_B2(bf16_t, 7);
-    }
-#undef CW_B2
-    return -1;
-  }
-  if (stride != 1) return -1;
-#define CW_B(TT, KV) return cw_launch_bwd<TT, KV>(gup, gss, yraw, yrss, c1, c2, c3, x, xss, sc, sh, relu, w, ldw, h, hss, dw, stats, stat_ld, part_rows, dw_ws, N, H, W, C, st)
-  if (dtype == DT_F32) {
-    if (k == 3) CW_B(float, 3); if (k == 5) CW_B(float, 5); if (k == 7) CW_B(float, 7);
-  } else {
-    if (k == 3) CW_B(bf16_t, 3); if (k == 5) CW_B(bf16_t, 5); if (k == 7) CW_B(bf16_t, 7);
-  }
-#undef CW_B
-  return -1;
-}
-
-int dwconv_cw_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                  float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st) {
-  if (!(cw_mode() & 2) || xss == 0 || yss == 0 || ldw < ((C + 7) & ~7)) return -1;
-#define CW_F(TT, KV) return cw_launch_fwd<TT, KV>(x, xss, sc, sh, relu, w, ldw, y, yss, stats, stat_ld, stat_rows, N, H, W, C, st)
-  if (dtype == DT_F32) {
-    if (k == 3) CW_F(float, 3); if (k == 5) CW_F(float, 5); if (k == 7) CW_F(float, 7);
-  } else {
-    if (k == 3) CW_F(bf16_t, 3); if (k == 5) CW_F(bf16_t, 5); if (k == 7) CW_F(bf16_t, 7);
-  }
-#undef CW_F
-  return -1;
+int cw_launch_bwd(const DwPlan& p, const DwBwdArgs& a) {
+  CwGeom g = p.g;
+  const bool s2 = a.s.stride == 2;
+  dw_for_type(a.s.dtype, [&](auto tt) {
+    dw_for_k(a.s.k, [&](auto kc) {
+      dw_for_act<false>(a.relu, false, [&](auto am) {
+        typedef typename decltype(tt)::type T;
+        constexpr int K = decltype(kc)::value, AM = decltype(am)::value;
+        // waves per SIMD the stride-1 instances are compiled for: 3 (k = 3: 139 registers) or 2
+        auto kern = s2 ? k_dwb_cw2<T, K, AM, 4, 2> : k_dwb_cw<T, K, AM, 4, (K == 3 ? 3 : 2), (K == 7)>;
+        cw_workers(g, resident_per_cu(kern, 256, p.lds), (a.stats || a.dw) ? a.part_rows : 0);
+        hipLaunchKernelGGL(kern, dim3(cw_grid(g)), dim3(256), p.lds, a.st, (const T*)a.gup, a.gss, (const T*)a.yraw, a.yrss, a.c1, a.c2,
+                           a.c3, (const T*)a.x, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw, (T*)a.h, a.hss, a.dw ? a.dw_ws : nullptr, a.stats,
+                           a.stat_ld, a.part_rows, g);
+      });
+    });
+  });
+  return dw_finish_bwd(s2 ? "dwconv_bwd(cw2)" : "dwconv_bwd(cw)", a, g.nworkers);
 }
 
 }  // namespace atomnas
@@ -988,21 +916,3 @@ extern "C" int atomnas_debug_cw_timing(unsigned long long* out8, int reset) {
   return 0;
 }
 #endif
-
-// 1 when atomnas_dwconv_fwd (dir = 0) / atomnas_dwconv_bwd (dir = 1) take the channel-pair-per-wave kernels of this file for the
-// shape (slab-major tensors, stride 1), 0 when they take the tile kernels of dwconv.hip.  Tests and launch-geometry tools only.
-extern "C" int atomnas_dwconv_cw_supported(int N, int H, int W, int C, int k, int stride, int dtype, int dir) {
-  using namespace atomnas;
-  if (!(k == 3 || k == 5 || k == 7)) return 0;
-  CwGeom g;
-  if (stride == 2) {
-    if (!(cw_mode() & (dir ? 4 : 8)) || dir == 0) return 0;   // stride 2: backward only so far
-    if (!cw2_geometry(g, N, H, W, C, k)) return 0;
-    const size_t lds = dtype == DT_F32 ? cw_lds<float>(g, 4) : cw_lds<bf16_t>(g, 4);
-    return lds <= max_lds_bytes() ? 1 : 0;
-  }
-  if (stride != 1 || !(cw_mode() & (dir ? 1 : 2))) return 0;
-  if (!cw_geometry(g, N, H, W, C, k)) return 0;
-  const size_t lds = dtype == DT_F32 ? cw_lds<float>(g, cw_nw()) : cw_lds<bf16_t>(g, cw_nw());
-  return lds <= max_lds_bytes() ? 1 : 0;
-}

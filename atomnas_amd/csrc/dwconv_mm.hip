@@ -26,7 +26,7 @@
 // would have the range but 2^-9 per operand; the inputs here are BatchNorm outputs behind an activation (O(1), not driven to zero by
 // the L1 penalty, which acts on the BatchNorm AFTER this convolution).  The fp32 parity mode never takes these kernels.
 // oracle/atomnas_oracle.py restates the two roundings (Bf16Storage(dw_fp16=True)).  Bit-reproducible; no atomics.
-#include "dwconv_cw.h"
+#include "dwconv_host.h"
 
 namespace atomnas {
 
@@ -34,13 +34,6 @@ typedef _Float16 f16_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 constexpr int MM_MAXG = 4;   // MFMA tile groups (16 tiles each) of a pixel tile: the per-lane decode of a group lives in registers
-
-// extra geometry of the matrix-core kernels on top of CwGeom (tiles, workers and the staging slots are dwconv_cw.hip's)
-struct MmGeom {
-  int nrp, ncb, ntl, ngroups;   // row pairs / 8-column blocks per image of the pixel tile, MFMA tiles per pixel tile, groups of 16
-  int nkb, xwp, xplane, steps;  // backward: 8-column blocks of a window row, row pitch / plane elements of the activated-input copies,
-                                // groups of four rows of the pixel tile (weight gradient: nkb MFMAs per group)
-};
 
 __device__ __forceinline__ float mm_clamp16(float a) { return __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f); }
 
@@ -699,107 +692,48 @@ static bool mm_geometry(CwGeom& g, MmGeom& mg, int N, int H, int W, int C, int K
   return mg.ngroups <= MM_MAXG;
 }
 
-static int mm_mode() {
-  // bits 0-2: forward k = 3 / 5 / 7, bits 3-5: backward k = 3 / 5 / 7, bit 6: backward also on whole-image tiles (14 x 14, 7 x 7 maps).
-  // Default (profiles/r05_dw_mm_per_shape.txt, batch 256): forward k = 5, 7 everywhere (k = 3 is as fast on the packed-FMA rows);
-  // backward k = 7 on row-ring tiles (56 x 56: 0.42 -> 0.34 ms, 28 x 28: 0.20 -> 0.16 ms) -- a tile of the backward kernel costs about
-  // the same for every k (commit + two operand copies + epilogue, ~1000 instructions per wave), which beats the packed-FMA rows only
-  // at k = 7 and only where a worker walks many tiles.
-  static const int m = getenv("ATOMNAS_DW_MM") ? atoi(getenv("ATOMNAS_DW_MM")) : 38;
-  return m;
-}
+// backward: the switch bit of k, and row-ring tiles unless bit 6 asks for whole-image tiles as well (dw_env, dwconv_host.h)
 static bool mm_bwd_wanted(const CwGeom& g, int k) {
   const int bit = k == 3 ? 8 : (k == 5 ? 16 : 32);
-  return (mm_mode() & bit) && (g.ring || (mm_mode() & 64));
+  return (dw_env().mm & bit) && (g.ring || (dw_env().mm & 64));
 }
 
-template <int K>
-static int mm_launch_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                         float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  MmGeom mg;
-  if (!mm_geometry(g, mg, N, H, W, C, K, false)) return -1;
-  const size_t lds = mm_lds(g, mg, K, false);
-  if (lds > max_lds_bytes()) return -1;
-#define MM_FWD(AMV)                                                                                                         \
-  {                                                                                                                         \
-    auto kern = k_dwf_mm<K, AMV, 4>;                                                                                        \
-    cw_workers(g, resident_per_cu(kern, 256, lds), stats ? stat_rows : 0, 4);                                               \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, 4)), dim3(256), lds, st, (const bf16_t*)x, xss, sc, sh, relu, w, ldw, (bf16_t*)y, yss, \
-                       stats, stat_ld, stat_rows, g, mg);                                                                   \
-  }
-  if (relu == ACT_RELU6) MM_FWD(ACT_RELU6) else if (relu == ACT_SWISH) MM_FWD(ACT_SWISH) else if (relu == ACT_RELU && sc) MM_FWD(ACT_RELU) else MM_FWD(0)
-#undef MM_FWD
+bool mm_plan(const DwShape& s, int dir, DwPlan& p) {
+  if (!s.slab || s.dtype != DT_BF16 || s.stride != 1) return false;
+  if (!mm_geometry(p.g, p.mg, s.N, s.H, s.W, s.C, s.k, dir != 0)) return false;
+  const int fwd_bit = s.k == 3 ? 1 : (s.k == 5 ? 2 : 4);
+  if (dir ? !mm_bwd_wanted(p.g, s.k) : !(dw_env().mm & fwd_bit)) return false;
+  p.lds = mm_lds(p.g, p.mg, s.k, dir != 0);
+  return p.lds <= max_lds_bytes();
+}
+
+int mm_launch_fwd(const DwPlan& p, const DwFwdArgs& a) {
+  CwGeom g = p.g;
+  dw_for_k(a.s.k, [&](auto kc) {
+    dw_for_act<true>(a.relu, a.sc != nullptr, [&](auto am) {
+      auto kern = k_dwf_mm<decltype(kc)::value, decltype(am)::value, 4>;
+      cw_workers(g, resident_per_cu(kern, 256, p.lds), a.stats ? a.stat_rows : 0);
+      hipLaunchKernelGGL(kern, dim3(cw_grid(g)), dim3(256), p.lds, a.st, (const bf16_t*)a.x, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw,
+                         (bf16_t*)a.y, a.yss, a.stats, a.stat_ld, a.stat_rows, g, p.mg);
+    });
+  });
   return check_launch("dwconv_fwd(mm)");
 }
 
-// -1: not one of this file's cases (the caller continues with dwconv_cw.hip / dwconv.hip); otherwise the launch status
-int dwconv_mm_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                  float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st) {
-  if (dtype != DT_BF16 || xss == 0 || yss == 0 || ldw < ((C + 7) & ~7)) return -1;
-  const int bit = k == 3 ? 1 : (k == 5 ? 2 : 4);
-  if (!(mm_mode() & bit)) return -1;
-#define MM_F(KV) return mm_launch_fwd<KV>(x, xss, sc, sh, relu, w, ldw, y, yss, stats, stat_ld, stat_rows, N, H, W, C, st)
-  if (k == 3) MM_F(3);
-  if (k == 5) MM_F(5);
-  if (k == 7) MM_F(7);
-#undef MM_F
-  return -1;
-}
-
-template <int K>
-static int mm_launch_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                         const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                         float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  MmGeom mg;
-  if (!mm_geometry(g, mg, N, H, W, C, K, true) || !mm_bwd_wanted(g, K)) return -1;
-  const size_t lds = mm_lds(g, mg, K, true);
-  if (lds > max_lds_bytes()) return -1;
-  const bool two = mg.ngroups <= 2;   // row-ring tiles have at most two MFMA tile groups: the instance with two per-lane decodes (10 registers less: no spill at k = 7)
-#define MM_BWD(AMV)                                                                                                         \
-  {                                                                                                                         \
-    auto kern = two ? k_dwb_mm<K, AMV, 3, 2> : k_dwb_mm<K, AMV, 3, MM_MAXG>;                                                                                      \
-    cw_workers(g, resident_per_cu(kern, 256, lds), (stats || dw) ? part_rows : 0, 4);                                       \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, 4)), dim3(256), lds, st, (const bf16_t*)gup, gss, (const bf16_t*)yraw, yrss, c1, c2, c3, \
-                       (const bf16_t*)x, xss, sc, sh, relu, w, ldw, (bf16_t*)h, hss, dw ? dw_ws : nullptr, stats, stat_ld, part_rows, g, mg); \
-  }
-  if (relu == ACT_RELU6) MM_BWD(ACT_RELU6) else if (relu == ACT_SWISH) MM_BWD(ACT_SWISH) else if (relu == ACT_RELU && sc) MM_BWD(ACT_RELU) else MM_BWD(0)
-#undef MM_BWD
-  if (int rc = check_launch("dwconv_bwd(mm)")) return rc;
-  if (dw) return reduce_parts(dw_ws, (long)C * K * K, g.nworkers, (long)C * K * K, dw, C * K * K, 0, 1, st);
-  return 0;
-}
-
-int dwconv_mm_bwd(const void* gup, long gss, const void* yraw, long yrss, const float* c1, const float* c2, const float* c3,
-                  const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* h, long hss,
-                  float* dw, float* stats, int stat_ld, int part_rows, float* dw_ws, int N, int H, int W, int C, int k, int stride,
-                  int dtype, hipStream_t st) {
-  if (dtype != DT_BF16 || stride != 1 || gss == 0 || xss == 0 || hss == 0 || (yraw && yrss == 0) || ldw < ((C + 7) & ~7)) return -1;
-#define MM_B(KV) return mm_launch_bwd<KV>(gup, gss, yraw, yrss, c1, c2, c3, x, xss, sc, sh, relu, w, ldw, h, hss, dw, stats, stat_ld, part_rows, dw_ws, N, H, W, C, st)
-  if (k == 3) MM_B(3);
-  if (k == 5) MM_B(5);
-  if (k == 7) MM_B(7);
-#undef MM_B
-  return -1;
-}
-
-int dwconv_mm_supported(int N, int H, int W, int C, int k, int dir) {
-  CwGeom g;
-  MmGeom mg;
-  if (!(k == 3 || k == 5 || k == 7)) return 0;
-  const int bit = k == 3 ? 1 : (k == 5 ? 2 : 4);
-  if (!mm_geometry(g, mg, N, H, W, C, k, dir != 0)) return 0;
-  if (dir ? !mm_bwd_wanted(g, k) : !(mm_mode() & bit)) return 0;
-  return mm_lds(g, mg, k, dir != 0) <= max_lds_bytes() ? 1 : 0;
+int mm_launch_bwd(const DwPlan& p, const DwBwdArgs& a) {
+  CwGeom g = p.g;
+  const bool two = p.mg.ngroups <= 2;   // row-ring tiles have at most two MFMA tile groups: the instance with two per-lane decodes (10 registers less: no spill at k = 7)
+  dw_for_k(a.s.k, [&](auto kc) {
+    dw_for_act<true>(a.relu, a.sc != nullptr, [&](auto am) {
+      constexpr int K = decltype(kc)::value, AM = decltype(am)::value;
+      auto kern = two ? k_dwb_mm<K, AM, 3, 2> : k_dwb_mm<K, AM, 3, MM_MAXG>;
+      cw_workers(g, resident_per_cu(kern, 256, p.lds), (a.stats || a.dw) ? a.part_rows : 0);
+      hipLaunchKernelGGL(kern, dim3(cw_grid(g)), dim3(256), p.lds, a.st, (const bf16_t*)a.gup, a.gss, (const bf16_t*)a.yraw, a.yrss, a.c1,
+                         a.c2, a.c3, (const bf16_t*)a.x, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw, (bf16_t*)a.h, a.hss,
+                         a.dw ? a.dw_ws : nullptr, a.stats, a.stat_ld, a.part_rows, g, p.mg);
+    });
+  });
+  return dw_finish_bwd("dwconv_bwd(mm)", a, g.nworkers);
 }
 
 }  // namespace atomnas
-
-// 1 when atomnas_dwconv_fwd (dir = 0) / atomnas_dwconv_bwd (dir = 1) take the matrix-core kernels of this file for the shape (bf16
-// slab-major tensors; stride 2: the forward of dwconv_mm2.hip).  Tests build the oracle's storage model from it (oracle/atomnas_oracle.py bf16_storage_mm).
-extern "C" int atomnas_dwconv_mm_supported(int N, int H, int W, int C, int k, int stride, int dtype, int dir) {
-  if (dtype != atomnas::DT_BF16) return 0;
-  if (stride == 2) return dir == 0 ? atomnas::dwconv_mm2_supported(N, H, W, C, k) : 0;
-  return stride == 1 ? atomnas::dwconv_mm_supported(N, H, W, C, k, dir) : 0;
-}

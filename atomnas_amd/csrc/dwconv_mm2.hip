@@ -19,7 +19,7 @@
 //
 // Numerics are dwconv_mm.hip's forward: fp16 operands (activated input, taps), exact products, fp32 accumulation, bf16 output;
 // oracle/atomnas_oracle.py restates the roundings (bf16_storage_mm).  Bit-reproducible; no atomics.
-#include "dwconv_cw.h"
+#include "dwconv_host.h"
 
 namespace atomnas {
 
@@ -28,11 +28,6 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 constexpr int M2_MAXG = 2;   // MFMA tile groups (16 tiles each) of a pixel tile
 constexpr int M2_XS = 7;     // staging slots (input pieces) per thread and tile: 4 x the (<= 448) output pixels / 256 threads
-
-struct Mm2Geom {
-  int nrp, ncb, ntl, ngroups;   // row pairs / 8-column blocks of the OUTPUT band per image, MFMA tiles per pixel tile, groups of 16
-  int TPIXDp;                   // pitch of the output pixel planes
-};
 
 __device__ __forceinline__ float mm2_clamp16(float a) { return __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f); }
 
@@ -386,50 +381,25 @@ static bool mm2_geometry(CwGeom& g, Mm2Geom& mg, int N, int H, int W, int C, int
   return K > 3 || g.tiles_y > 2;
 }
 
-static int mm2_mode() {
-  // bit 7 of ATOMNAS_DW_MM (see dwconv_mm.hip): the stride-2 forward on the matrix cores
-  static const int m = getenv("ATOMNAS_DW_MM") ? atoi(getenv("ATOMNAS_DW_MM")) : 128;
-  return m & 128;
+bool mm2_plan(const DwShape& s, int dir, DwPlan& p) {
+  if (dir != 0 || s.stride != 2 || !s.slab || s.dtype != DT_BF16 || !(dw_env().mm & 128)) return false;
+  if (!mm2_geometry(p.g, p.mg2, s.N, s.H, s.W, s.C, s.k)) return false;
+  p.lds = mm2_lds(p.g, p.mg2, s.k);
+  return p.lds <= max_lds_bytes();
 }
 
-template <int K>
-static int mm2_launch_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                          float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, hipStream_t st) {
-  CwGeom g;
-  Mm2Geom mg;
-  if (!mm2_geometry(g, mg, N, H, W, C, K)) return -1;
-  const size_t lds = mm2_lds(g, mg, K);
-  if (lds > max_lds_bytes()) return -1;
-#define MM2_FWD(AMV)                                                                                                        \
-  {                                                                                                                         \
-    auto kern = mg.ngroups == 1 ? k_dwf_mm2<K, AMV, 2, 1> : k_dwf_mm2<K, AMV, 2, 2>;                                        \
-    cw_workers(g, resident_per_cu(kern, 256, lds), stats ? stat_rows : 0, 4);                                               \
-    hipLaunchKernelGGL(kern, dim3(cw_grid(g, 4)), dim3(256), lds, st, (const bf16_t*)x, xss, sc, sh, relu, w, ldw, (bf16_t*)y, yss, \
-                       stats, stat_ld, stat_rows, g, mg);                                                                   \
-  }
-  if (relu == ACT_RELU6) MM2_FWD(ACT_RELU6) else if (relu == ACT_SWISH) MM2_FWD(ACT_SWISH) else if (relu == ACT_RELU && sc) MM2_FWD(ACT_RELU) else MM2_FWD(0)
-#undef MM2_FWD
+int mm2_launch_fwd(const DwPlan& p, const DwFwdArgs& a) {
+  CwGeom g = p.g;
+  dw_for_k(a.s.k, [&](auto kc) {
+    dw_for_act<true>(a.relu, a.sc != nullptr, [&](auto am) {
+      constexpr int K = decltype(kc)::value, AM = decltype(am)::value;
+      auto kern = p.mg2.ngroups == 1 ? k_dwf_mm2<K, AM, 2, 1> : k_dwf_mm2<K, AM, 2, 2>;
+      cw_workers(g, resident_per_cu(kern, 256, p.lds), a.stats ? a.stat_rows : 0);
+      hipLaunchKernelGGL(kern, dim3(cw_grid(g)), dim3(256), p.lds, a.st, (const bf16_t*)a.x, a.xss, a.sc, a.sh, a.relu, a.w, a.ldw,
+                         (bf16_t*)a.y, a.yss, a.stats, a.stat_ld, a.stat_rows, g, p.mg2);
+    });
+  });
   return check_launch("dwconv_fwd(mm2)");
-}
-
-// -1: not one of this file's cases (the caller continues with the tile kernels of dwconv.hip); otherwise the launch status
-int dwconv_mm2_fwd(const void* x, long xss, const float* sc, const float* sh, int relu, const float* w, int ldw, void* y, long yss,
-                   float* stats, int stat_ld, int stat_rows, int N, int H, int W, int C, int k, int dtype, hipStream_t st) {
-  if (dtype != DT_BF16 || xss == 0 || yss == 0 || ldw < ((C + 7) & ~7) || !mm2_mode()) return -1;
-#define MM2_F(KV) return mm2_launch_fwd<KV>(x, xss, sc, sh, relu, w, ldw, y, yss, stats, stat_ld, stat_rows, N, H, W, C, st)
-  if (k == 3) MM2_F(3);
-  if (k == 5) MM2_F(5);
-  if (k == 7) MM2_F(7);
-#undef MM2_F
-  return -1;
-}
-
-int dwconv_mm2_supported(int N, int H, int W, int C, int k) {
-  CwGeom g;
-  Mm2Geom mg;
-  if (!(k == 3 || k == 5 || k == 7) || !mm2_mode()) return 0;
-  if (!mm2_geometry(g, mg, N, H, W, C, k)) return 0;
-  return mm2_lds(g, mg, k) <= max_lds_bytes() ? 1 : 0;
 }
 
 }  // namespace atomnas

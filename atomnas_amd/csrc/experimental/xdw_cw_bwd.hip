@@ -1,7 +1,7 @@
 // Round-4 experiment, NOT part of the product library (built by tools/build_xdw_experiment.sh only): the channel-pair depthwise
 // backward with its input operand E = x We^T recomputed on chip ("E-elimination"; measured slower than
 // reading E).  Moved out of csrc/dwconv_cw.hip in round 5; entry points declared in xdw_experimental.h / used by xdw_fused.hip.
-#include "../dwconv_cw.h"
+#include "../dwconv_host.h"
 #include "xdw_internal.h"
 
 #undef CW_TIMING
@@ -410,7 +410,7 @@ static int xdw_launch_bwd(const void* gup, long gss, const void* yraw, long yrss
 #define XDW_BWD(AMV)                                                                                                          \
   {                                                                                                                           \
     auto kern = k_xdwb<K, AMV, KC, WPSV, (K == 7)>;                                                                           \
-    cw_workers(g, resident_per_cu(kern, 256, lds), (stats || dw) ? part_rows : 0, 4);                                         \
+    cw_workers(g, resident_per_cu(kern, 256, lds), (stats || dw) ? part_rows : 0);                                            \
     hipLaunchKernelGGL(kern, dim3((unsigned)(((g.nworkers * g.nslabs + 7) / 8) * 16)), dim3(256), lds, st, (const bf16_t*)gup, gss, (const bf16_t*)yraw, yrss, c1, c2, c3, \
                        (const bf16_t*)xin, ldx, inp, (const bf16_t*)wexp, ldwe, sc, sh, relu, w, ldw, (bf16_t*)h, hss,       \
                        dw ? dw_ws : nullptr, stats, stat_ld, part_rows, g);                                                   \
