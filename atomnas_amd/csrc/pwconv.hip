@@ -327,9 +327,6 @@ enum { ST_FWD = 1, ST_MASK = 2, ST_PBWD = 3 };
 #ifndef ST_SHARED
 #define ST_SHARED 1
 #endif
-#ifndef ST_STORE_SOFFSET
-#define ST_STORE_SOFFSET 0   // experiment builds: 1 = the tile offset of the output stores in an SGPR soffset (round 3/4 form)
-#endif
 #ifndef ST_BT6
 #define ST_BT6 4   // six k-steps (K = 192): bursts only in the shared form (one tile is already a 6 KB request: per-tile ring otherwise)
 #endif
@@ -542,19 +539,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
       for (int i = 0; i < 8; ++i) ob[i] = (bf16_t)c[8 * h + i];
       u32x4 obits = __builtin_bit_cast(u32x4, ob);
       asm volatile("" : "+v"(obits));   // the packed conversion happens once (common.h: bf16_pair_f32)
-      // The tile offset rides in soffset (one scalar for all unrolled tiles instead of a vector induction variable per access and
-      // tile).  HAZARD: with an SGPR soffset LLVM does not keep the next VALU instructions off the store's data registers (its rule
-      // exempts that form), but on gfx950 data overwritten in the two instructions after the store IS what gets written (r03: 0.17 %
-      // wrong elements in test_gemm_nt[20000-1440-80]).  The asm below uses `ob` after the statistics: its registers stay intact.
-#if ST_STORE_SOFFSET
-      __builtin_amdgcn_raw_buffer_store_b128(obits, rc, rv ? c_lane[h] : ST_OOB, (unsigned)t * c_tile, 0);
-#else
-      // round 5: the tile offset is added to the vector offset (soffset 0).  With the scalar offset the hazard above is NOT bounded by
-      // two instructions: at M = 12544, N = 3456, K = 192 (the 7x7 expand, store queue backed up) the first data dword of a store was
-      // replaced by a value written to that register ~28 instructions later (the next store's offset), 4 lanes at a time, ~4000 of 43 M
-      // outputs per launch, different ones in every run (tools/gemmcheck.py, profiles/r05_st_store_hazard.txt).
+      // The tile offset is added to the vector offset (soffset 0).  HAZARD of the form with the tile offset in an SGPR soffset (rounds
+      // 3 / 4: one scalar for all unrolled tiles): LLVM does not keep the next VALU instructions off that store's data registers (its
+      // rule exempts that form), but on gfx950 data overwritten after the store IS what gets written -- r03: 0.17 % wrong elements in
+      // test_gemm_nt[20000-1440-80]; r05, at M = 12544, N = 3456, K = 192 (the 7x7 expand, store queue backed up): the first data dword
+      // of a store was replaced by a value written to that register ~28 instructions later (the next store's offset), 4 lanes at a
+      // time, ~4000 of 43 M outputs per launch, different ones in every run (tools/gemmcheck.py, profiles/r05_st_store_hazard.txt).
+      // The asm below uses `ob` after the statistics: its registers stay intact.
       __builtin_amdgcn_raw_buffer_store_b128(obits, rc, rv ? c_lane[h] + (unsigned)t * c_tile : ST_OOB, 0, 0);
-#endif
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const f32x2 o = bf16_pair_f32(obits[i]);   // statistics see the stored value
@@ -1098,13 +1090,10 @@ __global__ __launch_bounds__(256) void k_gemm_nt_ws(Operand A, const bf16_t* __r
 #endif
 constexpr int XB_DP = 64 + 8;   // transposed LDS pitch (elements): rows of the block + pad; 144 bytes, 16-byte aligned rows
 
-#ifndef EB_MINWG
-#define EB_MINWG 2   // workgroups per CU the registers are allocated for (experiment switch)
-#endif
 // dE = c1*h only (round 4; the two-stream form that read the raw expand output E as well was removed in round 6): the c2*E + c3 part
 // of the BatchNorm backward reaches dX / dWe through inp x inp sized corrections (atomnas_xb_coeffs), so E is not read.
 template <int UT, int NCH>
-__global__ __launch_bounds__(256, EB_MINWG) void k_expand_bwd(Operand A, const bf16_t* __restrict__ Wp, int ldw, int wrows, const bf16_t* __restrict__ x,
+__global__ __launch_bounds__(256, 2) void k_expand_bwd(Operand A, const bf16_t* __restrict__ Wp, int ldw, int wrows, const bf16_t* __restrict__ x,
                                                     int ldx, Epilogue ep, float* __restrict__ ws, long M, int N, int K,
                                                     const bf16_t* __restrict__ mpk, int ldm) {
   using T = bf16_t;
@@ -1294,98 +1283,6 @@ __global__ __launch_bounds__(256, EB_MINWG) void k_expand_bwd(Operand A, const b
   }
 }
 
-// ------------------------------------------------------------------------------------------------ host side
-// The streaming instances take the cases they are written for (see k_gemm_nt_st); everything else goes on to the LDS-weights / generic kernels.
-static int nt_st_kind(int mode, const Operand& A, const Epilogue& ep, long M, int N, int K) {
-  static const int on = getenv("ATOMNAS_NT_ST") ? atoi(getenv("ATOMNAS_NT_ST")) : 1;
-  if (!on || mode != PRO_NONE || (K & 7) || ep.bias || ep.add || ep.out_f32) return 0;
-  const bool stats = ep.stats != nullptr && ep.stat_mode != STAT_NONE;
-  if (ep.stats != nullptr && ep.stat_mode == STAT_NONE) return 0;
-  // a row range is at most 4096 tiles (32-bit tile offsets) and owns one partial row of the statistics
-  if (stats && ((M + 15) / 16 + ep.stat_rows - 1) / ep.stat_rows > 4096) return 0;
-  // 32-bit byte offsets below 2^31 inside the per-wave resources: the whole A tensor, four slabs (one chunk) of C and z
-  const long a_bytes = A.ss1 ? ((long)((K + 15) / 16 - 1) * A.ss1 + M * 16) * 2 : M * (long)A.ld1 * 2;
-  if (a_bytes >= (1L << 31)) return 0;
-  if (ep.css ? (3 * ep.css + M * 16) * 2 >= (1L << 31) : ((N & 7) || (long)ep.ldc * 2 * 16 * 4096 >= (1L << 31))) return 0;
-  if (!ep.z) return (!stats || ep.stat_mode == STAT_SQ) ? ST_FWD : 0;
-  if (!ep.mask || (stats && ep.stat_mode != STAT_Z)) return 0;
-  if (ep.zss ? (3 * ep.zss + M * 16) * 2 >= (1L << 31) : ((N & 7) || (long)ep.ldz * 2 * 16 * 4096 >= (1L << 31))) return 0;
-  return ST_MASK;
-}
-
-template <int KSTEPS>
-static void launch_nt_st(int kind, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
-  const int nchunks = (N + 63) / 64;
-  const long mtiles = (M + 15) / 16;
-  const bf16_t* W = (const bf16_t*)Wp;
-  const long min_tpi = ep.stats ? (mtiles + ep.stat_rows - 1) / ep.stat_rows : 1;   // every row range owns one partial row
-#define ST_LAUNCH(EPKV, SHV, BTV)                                                                                         \
-  {                                                                                                                     \
-    using Cfg = StCfg<KSTEPS, EPKV>;                                                                                    \
-    auto kern = k_gemm_nt_st<KSTEPS, EPKV, Cfg::PD, BTV, Cfg::WPE, 0, SHV>;                                            \
-    const size_t lds = (size_t)(SHV ? 2 : 4) * (BTV) * KSTEPS * 1024 + (EPKV == ST_FWD ? 0 : (size_t)4 * (16 + 64) * PB_RP * sizeof(bf16_t) + 4 * 128 * sizeof(float)); /* burst staging (+ z coefficients) */ \
-    const long waves = (long)num_cus() * resident_per_cu(kern, 256, lds) * 4;                                           \
-    const long wchunks = SHV ? (long)((nchunks + 3) / 4) * 4 : nchunks;   /* wave slots per row range */                \
-    long tiles_per_item = (mtiles * wchunks + waves - 1) / waves;                                                       \
-    if (tiles_per_item < 8) tiles_per_item = 8;                                                                         \
-    if (tiles_per_item < min_tpi) tiles_per_item = min_tpi;                                                             \
-    const long max_ranges = waves / wchunks > 0 ? waves / wchunks : 1;   /* one round of workgroups */ \
-    if ((mtiles + tiles_per_item - 1) / tiles_per_item > max_ranges) tiles_per_item = (mtiles + max_ranges - 1) / max_ranges; \
-    if (tiles_per_item > 4096) tiles_per_item = 4096;   /* keeps t * tile bytes in 32 bits (nt_st_kind) */              \
-    const long nrg = (mtiles + tiles_per_item - 1) / tiles_per_item;                                                    \
-    const long blocks = SHV ? nrg * ((nchunks + 3) / 4) : (nrg * nchunks + 3) / 4;                                      \
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, A, W, ldw, ep, M, N, K, nchunks, (int)tiles_per_item, (float*)nullptr); \
-  }
-  // Bursts shared by the four waves of a workgroup (one read of the narrow operand per workgroup instead of per wave) where whole
-  // groups of four chunks waste at most 5 % of the wave slots: 14x14 (23 / 27 chunks) -10..-18 %, 28x28 (12) equal; with 5 or 7 chunks
-  // the repeated chunk costs more than the sharing saves (112x112 +38 %, 56x56 masked form +15 %; r03, tools/pwbench.py).
-#define ST_CASE(EPKV)                                                                                                   \
-  {                                                                                                                     \
-    const bool shared = StCfg<KSTEPS, EPKV>::SH && ((nchunks + 3) / 4 * 4 - nchunks) * 20 <= nchunks;                   \
-    if (shared) ST_LAUNCH(EPKV, (StCfg<KSTEPS, EPKV>::SH), (StCfg<KSTEPS, EPKV>::BT))                                   \
-    else ST_LAUNCH(EPKV, false, (StCfg<KSTEPS, EPKV>::BTP))                                                            \
-  }
-  if (kind == ST_FWD) ST_CASE(ST_FWD) else ST_CASE(ST_MASK)
-#undef ST_LAUNCH
-#undef ST_CASE
-}
-
-static int launch_nt_ws(int mode, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
-  const bf16_t* W = (const bf16_t*)Wp;
-  const int wrows = (N + 63) / 64 * 64;   // rows of the packed weight matrix
-  const int ncg = N > 64 ? 2 : 1;
-  const int ngroups = (N + 64 * ncg - 1) / (64 * ncg);
-  const bool do_stats = ep.stats && ep.stat_mode != STAT_NONE;
-  const size_t lds_stat = do_stats ? (size_t)8 * 64 * ncg * sizeof(float) : 0;
-  // two 16-row subtiles per wave (each weight fragment read feeds two MFMAs) when there are enough 128-row blocks
-  constexpr int rt_env = 0;
-  // measured in situ per shape (bs 256 step, same box, ATOMNAS_NT_WS_RT=1/2): one subtile per wave is faster wherever the prologue is
-  // BN-apply (the projection forward: M = 50176 -28 %, 200704 -15 %, 802816 -7 % -- the two-subtile BNRELU instance with two chunks
-  // needs 335 registers, one wave per SIMD) and on the small maps; two subtiles only pay with the two-stream BN-backward prologue
-  // on the large maps (M = 200704: -3 %)
-  const int rt = rt_env ? rt_env : ((mode == PRO_BNBWD && M >= 100000) ? 2 : 1);
-#define WS_LAUNCH(MODE, NCGV, RTV)                                                                                       \
-  {                                                                                                                      \
-    auto kern = k_gemm_nt_ws<MODE, NCGV, RTV>;                                                                           \
-    const size_t lds = (size_t)2 * 64 * NCGV * WS_WP * sizeof(bf16_t) + 2 * 3 * WS_KC * sizeof(float) + lds_stat;        \
-    const long rblocks = (M + 64 * RTV - 1) / (64 * RTV);                                                                \
-    long R = (long)num_cus() * resident_per_cu(kern, 256, lds) / ngroups;   /* row slots: one round of resident workgroups */ \
-    if (R > rblocks) R = rblocks;                                                                                        \
-    if (do_stats && R > ep.stat_rows) R = ep.stat_rows;                                                                  \
-    if (R < 1) R = 1;                                                                                                    \
-    hipLaunchKernelGGL(kern, dim3((unsigned)(R * ngroups)), dim3(256), lds, st, A, W, ldw, wrows, ep, M, N, K);          \
-  }
-#define WS_MODE(MODE)                                                                  \
-  if (ncg == 1) { if (rt == 2) WS_LAUNCH(MODE, 1, 2) else WS_LAUNCH(MODE, 1, 1) }      \
-  else { if (rt == 2) WS_LAUNCH(MODE, 2, 2) else WS_LAUNCH(MODE, 2, 1) }
-  if (mode == PRO_NONE) { WS_MODE(PRO_NONE) }
-  else if (mode == PRO_BNRELU) { WS_MODE(PRO_BNRELU) }
-  else { WS_MODE(PRO_BNBWD) }
-#undef WS_MODE
-#undef WS_LAUNCH
-  return check_launch("gemm_nt_ws");
-}
-
 // ------------------------------------------------------------------------------------------------ streaming wide-input GEMM
 // C[M][N] = act(A * scale + shift) W^T for a NARROW output (N <= 48) of a wide slab-major input (K <= 448): the projection of the
 // early stages (models/mobilenet_base.py:338,378), with the statistics of the output's BatchNorm.  The structure of k_expand_bwd_s:
@@ -1564,34 +1461,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_sw(const bf16_t* __restrict_
       }
     }
   }
-}
-
-// -1: not this kernel's case (the caller goes on), otherwise the launch status
-static int launch_nt_sw(int mode, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
-  static const int on = getenv("ATOMNAS_NT_SW") ? atoi(getenv("ATOMNAS_NT_SW")) : 1;   // experiment switch
-  const bool do_stats = ep.stats && ep.stat_mode != STAT_NONE;
-  if (!on || mode != PRO_BNRELU || A.ss1 <= 0 || N > 48 || N % 8 != 0 || K > 448 || K < 97 || M < 16384 || ep.out_f32 || ep.css != 0 ||
-      ep.add || ep.z || ep.mask || ep.bias || (do_stats && ep.stat_mode != STAT_SQ))
-    return -1;
-  const int ut = (N + 15) / 16, nch = (K + 63) / 64 <= 5 ? 5 : 7;
-  const size_t fixed = (size_t)16 * ut * (nch * 64 + 8) * sizeof(bf16_t) + (size_t)2 * nch * 64 * sizeof(float) + (size_t)4 * 2 * 16 * ut * sizeof(float);
-  const int depth = 2 * (fixed + 4 * 8192) + 4096 <= max_lds_bytes() ? 4 : 3;
-  const size_t lds = fixed + (size_t)depth * 8192;
-  if (2 * lds + 2048 > max_lds_bytes()) return -1;
-  const long rblocks = (M + 63) / 64;
-#define SW_CASE(UTV, NCHV)                                                                                                              \
-  if (ut == UTV && nch == NCHV) {                                                                                                       \
-    auto kern = depth == 4 ? k_gemm_nt_sw<UTV, NCHV, 4> : k_gemm_nt_sw<UTV, NCHV, 3>;                                                   \
-    long R = (long)num_cus() * resident_per_cu(kern, 256, lds);                                                                         \
-    if (R > rblocks) R = rblocks;                                                                                                       \
-    if (do_stats && R > ep.stat_rows) R = ep.stat_rows;                                                                                 \
-    hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(256), lds, st, (const bf16_t*)A.p1, A.ss1, A.c1, A.c2, A.relu, (const bf16_t*)Wp, ldw, \
-                       (bf16_t*)ep.c, ep.ldc, do_stats ? ep.stats : nullptr, ep.stat_rows, M, N, K);                                    \
-    return check_launch("gemm_nt_sw");                                                                                                  \
-  }
-  SW_CASE(1, 5) SW_CASE(1, 7) SW_CASE(2, 5) SW_CASE(2, 7) SW_CASE(3, 5) SW_CASE(3, 7)
-#undef SW_CASE
-  return -1;
 }
 
 // ------------------------------------------------------------------------------------------------ streaming wide-input GEMM, late stages
@@ -1828,171 +1697,6 @@ __global__ __launch_bounds__(NWV * 64, WGPC) void k_gemm_nt_swg(const bf16_t* __
       }
     }
   }
-}
-
-template <int UT, int WGPC, int NWV>
-static int launch_swg(const bf16_t* a, long ass, const float* scale, const float* shift, int act, const bf16_t* W, int ldw, bf16_t* c, int ldc,
-                      float* stats, int stat_rows, long M, int N, int K, hipStream_t st) {
-  constexpr int DEPTH = 3;
-  const size_t lds = (size_t)NWV * 2 * 16 * UT * sizeof(float) + (size_t)DEPTH * (2 * NWV + 2 * UT + 1) * 1024;
-  if (lds > max_lds_bytes()) return -1;
-  auto kern = k_gemm_nt_swg<UT, DEPTH, WGPC, NWV>;
-  const long rblocks = (M + NWV * 16 - 1) / (NWV * 16);
-  long R = (long)num_cus() * resident_per_cu(kern, NWV * 64, lds);
-  if (R > rblocks) R = rblocks;
-  if (stats && R > stat_rows) R = stat_rows;
-  hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(NWV * 64), lds, st, a, ass, scale, shift, act, W, ldw, c, ldc, stats, stat_rows, M, N, K);
-  return check_launch("gemm_nt_swg");
-}
-
-
-// -1: not this kernel's case (the caller continues with k_gemm_nt_ws)
-static int launch_nt_swg(int mode, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
-  static const int on = getenv("ATOMNAS_NT_SWG") ? atoi(getenv("ATOMNAS_NT_SWG")) : 1;   // experiment switch (0: k_gemm_nt_ws)
-  const bool do_stats = ep.stats && ep.stat_mode != STAT_NONE;
-  // measured (r04 prototype, r05 in situ): gains at 14 x 14 and 7 x 7 (M <= 50176), none at 28 x 28 (M = 200704: every stage moves
-  // 12 KB of weights from L2 for 8 KB of activations) -- until round 6 took two thirds of the prologue's instructions out (common.h: Act):
-  // since then 0.098 -> 0.077 ms at M = 200704, N = 40, K = 720 (tools/pwbench.py project), and the row limit is 262144
-  static const long maxm = getenv("ATOMNAS_NT_SWG_MAXM") ? atol(getenv("ATOMNAS_NT_SWG_MAXM")) : 262144;   // experiment switch
-  if (!on || mode != PRO_BNRELU || A.ss1 <= 0 || N % 8 != 0 || N > 320 || K < 256 || K % 4 != 0 || M < 8192 || M > maxm || ldw < 64 || ldw % 8 != 0 ||
-      ep.out_f32 || ep.css != 0 || ep.add || ep.z || ep.mask || ep.bias || (do_stats && ep.stat_mode != STAT_SQ) || !A.c1 || !A.c2)
-    return -1;
-  const int ut = (N + 15) / 16;
-  // 128-row stages (eight waves, one weight chunk per 128 rows: half the weight traffic per activation byte) where they still fill the
-  // chip: 14 x 14 (392 workgroups); 64-row stages at 7 x 7 (196 workgroups of four waves)
-  const bool wide = (M + 127) / 128 >= num_cus() && ut <= 6;
-  float* stats = do_stats ? ep.stats : nullptr;
-#define SWG_ARGS (const bf16_t*)A.p1, A.ss1, A.c1, A.c2, A.relu, (const bf16_t*)Wp, ldw, (bf16_t*)ep.c, ep.ldc, stats, ep.stat_rows, M, N, K, st
-#define SWG_CASE(UTV, WG)                                   \
-  if (ut == UTV) {                                          \
-    if (wide) return launch_swg<UTV, 1, 8>(SWG_ARGS);       \
-    return launch_swg<UTV, WG, 4>(SWG_ARGS);                \
-  }
-  SWG_CASE(3, 2) SWG_CASE(5, 2) SWG_CASE(6, 2)
-  // wide outputs: four-wave stages only (an eight-wave instance would have 128 registers per lane for 2 x 16 UT accumulators and
-  // weight fragments: it spills, and a scratch reload inside the ring loop drains the queue -- tools/check_asm_waits.py flags it)
-  if (ut == 12) return launch_swg<12, 1, 4>(SWG_ARGS);
-  if (ut == 20) return launch_swg<20, 1, 4>(SWG_ARGS);
-#undef SWG_ARGS
-#undef SWG_CASE
-  return -1;
-}
-
-template <typename T>
-static int launch_nt(int mode, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
-    int rc = launch_nt_sw(mode, A, Wp, ldw, ep, M, N, K, st);   // narrow output of a wide slab-major input: the streaming kernel
-    if (rc >= 0) return rc;
-    rc = launch_nt_swg(mode, A, Wp, ldw, ep, M, N, K, st);      // late stages: weights in the queue
-    if (rc >= 0) return rc;
-  }
-  if constexpr (sizeof(T) == 2) {
-    // column-stationary form when the output is the wide operand
-    constexpr int cs_maxk = 192;
-    // with the BatchNorm-backward prologue the 6-k-step instance (K = 192: 7x7 maps) needs 256 + 49 registers, one wave per SIMD;
-    // the LDS-weights kernel is 10 % faster there (in situ, M = 12544, N = 3456 / 1728), without a prologue it is 50 % slower
-    constexpr int cs_maxk_pro = 96;
-    if (K <= (mode == PRO_BNBWD ? cs_maxk_pro : cs_maxk) && K <= 192 && N >= 2 * K && N >= 96 && M >= 1024) {
-      const int ksteps = (K + 31) / 32;
-      if (const int kind = nt_st_kind(mode, A, ep, M, N, K)) {
-        if (ksteps == 1) launch_nt_st<1>(kind, A, Wp, ldw, ep, M, N, K, st);
-        else if (ksteps == 2) launch_nt_st<2>(kind, A, Wp, ldw, ep, M, N, K, st);
-        else if (ksteps == 3) launch_nt_st<3>(kind, A, Wp, ldw, ep, M, N, K, st);
-        else launch_nt_st<6>(kind, A, Wp, ldw, ep, M, N, K, st);
-        return check_launch("gemm_nt_st");
-      }
-      // anything else in this shape class (a prologue, a bias / residual epilogue, K not a multiple of 8) takes the kernels below
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    constexpr int small_env = 1;
-    if (small_env && N <= 64 && K <= 64 && M >= 65536) {
-      const long mtiles = (M + 15) / 16;
-      const bool do_stats = ep.stats && ep.stat_mode != STAT_NONE;
-      const size_t lds = do_stats ? (size_t)8 * 64 * sizeof(float) : 0;
-      const bf16_t* W = (const bf16_t*)Wp;
-      // lanes own 4 channels x NT tiles where the output allows it (bf16, N a multiple of 4); ATOMNAS_NT_SMALL_NARROW=0: the 16-channel form
-      static const int narrow_on = getenv("ATOMNAS_NT_SMALL_NARROW") ? atoi(getenv("ATOMNAS_NT_SMALL_NARROW")) : 1;
-      const int ntile = (narrow_on && !ep.out_f32 && N % 4 == 0) ? (N <= 16 ? 1 : N <= 32 ? 2 : 4) : 0;
-#define SM_LAUNCH(MODE, KSTV)                                                                                  \
-  {                                                                                                            \
-    auto kern = ntile == 1 ? k_gemm_nt_small<MODE, KSTV, 1> : ntile == 2 ? k_gemm_nt_small<MODE, KSTV, 2>      \
-              : ntile == 4 ? k_gemm_nt_small<MODE, KSTV, 4> : k_gemm_nt_small<MODE, KSTV, 0>;                  \
-    long R = (long)num_cus() * resident_per_cu(kern, 256, lds);                                                \
-    if (R > (mtiles + 3) / 4) R = (mtiles + 3) / 4;                                                            \
-    if (do_stats && R > ep.stat_rows) R = ep.stat_rows;                                                        \
-    if (R < 1) R = 1;                                                                                          \
-    hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(256), lds, st, A, W, ldw, ep, M, N, K);                   \
-  }
-#define SM_CASE(MODE) \
-  if (K <= 32) SM_LAUNCH(MODE, 1) else SM_LAUNCH(MODE, 2)
-      if (mode == PRO_NONE) { SM_CASE(PRO_NONE) }
-      else if (mode == PRO_BNRELU) { SM_CASE(PRO_BNRELU) }
-      else { SM_CASE(PRO_BNBWD) }
-#undef SM_CASE
-#undef SM_LAUNCH
-      return check_launch("gemm_nt_small");
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    constexpr int ws_env = 1;
-    constexpr int ws_mink = 97;
-    if (ws_env && K >= ws_mink && M >= 4096) return launch_nt_ws(mode, A, Wp, ldw, ep, M, N, K, st);
-  }
-  constexpr int KS = 4 * Mma<T>::EPL;
-  const int Kpad = (K + KS - 1) / KS * KS;
-  const long mtiles = (M + 15) / 16;
-  const bool wide = N > 64;  // keep two 64-channel chunks live when there is more than one
-  const int ngroups = wide ? (N + 127) / 128 : 1;
-  const bool do_stats = ep.stats && ep.stat_mode != STAT_NONE;
-  const size_t lds = do_stats ? (size_t)8 * (wide ? 128 : 64) * sizeof(float) : 0;
-  const T* W = (const T*)Wp;
-  // persistent grid-stride loop over (row tile, channel group) items: one round of resident workgroups
-#define NT_LAUNCH(MODE, NCGV)                                                                                  \
-  {                                                                                                            \
-    auto kern = k_gemm_nt<T, MODE, NCGV>;                                                                      \
-    long R = (long)num_cus() * resident_per_cu(kern, 256, lds) / ngroups;   /* row slots of 4 tiles */         \
-    if (R > (mtiles + 3) / 4) R = (mtiles + 3) / 4;                                                            \
-    if (do_stats && R > ep.stat_rows) R = ep.stat_rows;                                                        \
-    if (R < 1) R = 1;                                                                                          \
-    hipLaunchKernelGGL(kern, dim3((unsigned)(R * ngroups)), dim3(256), lds, st, A, W, ldw, ep, M, N, K, Kpad); \
-  }
-#define NT_CASE(MODE) \
-  if (wide) NT_LAUNCH(MODE, 2) else NT_LAUNCH(MODE, 1)
-  if (mode == PRO_NONE) { NT_CASE(PRO_NONE) }
-  else if (mode == PRO_BNRELU) { NT_CASE(PRO_BNRELU) }
-  else { NT_CASE(PRO_BNBWD) }
-#undef NT_CASE
-#undef NT_LAUNCH
-  return check_launch("gemm_nt");
-}
-
-// fused project backward (column-stationary input gradient + weight gradient)
-// the streaming form of the fused projection backward: A is the materialised dP (atomnas_bnbwd_apply), no prologue
-template <int KSTEPS, int UT>
-static int launch_project_bwd_st(const Operand& A, const bf16_t* W, int ldw, const Epilogue& ep, float* dwp, long si, long sj, float* ws,
-                                 long ws_floats, long M, int N, int K, hipStream_t st) {
-  using Cfg = StCfg<KSTEPS, ST_PBWD>;
-  const int nchunks = (N + 63) / 64;
-  const long mtiles = (M + 15) / 16;
-  auto kern = k_gemm_nt_st<KSTEPS, ST_PBWD, Cfg::PD, Cfg::BT, Cfg::WPE, UT, false>;
-  const size_t lds = (size_t)4 * Cfg::BT * KSTEPS * 1024 + (size_t)4 * (16 * UT + 64) * PB_RP * sizeof(bf16_t) + 4 * 128 * sizeof(float);
-  const long waves = (long)num_cus() * resident_per_cu(kern, 256, lds) * 4;
-  long tiles_per_item = (mtiles * nchunks + waves - 1) / waves;
-  if (tiles_per_item < 8) tiles_per_item = 8;
-  const long min_tpi = (mtiles + ep.stat_rows - 1) / ep.stat_rows;   // every row range owns one partial row of the statistics
-  if (tiles_per_item < min_tpi) tiles_per_item = min_tpi;
-  const long max_parts = ws_floats / ((long)K * N);   // ... and one partial of the weight gradient
-  ATOMNAS_REQUIRE(max_parts >= 1, "project_bwd: workspace too small for one partial (%ld floats)", (long)K * N);
-  long max_ranges = waves / nchunks > 0 ? waves / nchunks : 1;
-  if (max_ranges > max_parts) max_ranges = max_parts;
-  if ((mtiles + tiles_per_item - 1) / tiles_per_item > max_ranges) tiles_per_item = (mtiles + max_ranges - 1) / max_ranges;
-  ATOMNAS_REQUIRE(tiles_per_item <= 4096, "project_bwd: %ld row tiles per work item (workspace / statistics rows too small for M=%ld)", tiles_per_item, M);
-  const long nranges = (mtiles + tiles_per_item - 1) / tiles_per_item;
-  const long items = nranges * nchunks;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, A, W, ldw, ep, M, N, K, nchunks, (int)tiles_per_item, ws);
-  if (int rc = check_launch("project_bwd_st")) return rc;
-  return reduce_parts(ws, (long)K * N, (int)nranges, (long)K * N, dwp, N, si, sj, st);
 }
 
 // ------------------------------------------------------------------------------------------------ streaming expand backward (e == NULL)
@@ -2248,51 +1952,433 @@ __global__ __launch_bounds__(256, 2) void k_expand_bwd_s(const bf16_t* __restric
   }
 }
 
-template <int UT, int NCH>
-static int launch_expand_bwd_s(const bf16_t* h, long hss, const float* c1, const bf16_t* W, int ldw, const bf16_t* x, int ldx,
-                               const bf16_t* add, int ldadd, bf16_t* gx, int ldgx, const bf16_t* mpk, int ldm, const float* vb, float* dwe,
-                               float* ws, long ws_floats, long M, int N, int K, hipStream_t st) {
-  // The x / residual tiles are double-buffered per row block: the copy for block b + 2 is issued DEPTH - 1 stages ahead of that block's
-  // first stage, which lies inside block b + 1 only if a block has at least DEPTH - 1 = 3 stages.  Narrower hidden tensors (K <= 128:
-  // one or two 64-channel chunks) take k_expand_bwd.
-  if ((K + 63) / 64 < 3) return -1;
-  const size_t fixed = (size_t)16 * UT * (NCH * 64 + 8) * sizeof(bf16_t) + (size_t)4 * 2 * UT * 1024;   // weights + x and residual tiles
-  const int depth = 2 * (fixed + 4 * 8192) + 4096 <= max_lds_bytes() ? 4 : 3;   // deepest ring that leaves room for two workgroups per CU
-  const size_t lds = fixed + (size_t)depth * 8192;
-  if (lds > max_lds_bytes()) return -1;
-  auto kern = depth == 4 ? k_expand_bwd_s<UT, NCH, 4> : k_expand_bwd_s<UT, NCH, 3>;
-  const long rblocks = (M + 63) / 64;
-  long R = (long)num_cus() * resident_per_cu(kern, 256, lds);   // one round of resident workgroups
-  if (R > rblocks) R = rblocks;
-  const long max_parts = ws_floats / ((long)N * K);   // every workgroup owns one partial of the weight gradient
-  if (R > max_parts) R = max_parts;
-  ATOMNAS_REQUIRE(R >= 1, "expand_bwd: workspace too small for one partial (%ld floats)", (long)N * K);
-  hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(256), lds, st, h, hss, c1, W, ldw, x, ldx, add, ldadd, gx, ldgx, mpk, ldm, vb, ws, M, N, K);
-  if (int rc = check_launch("expand_bwd(stream)")) return rc;
-  return reduce_parts(ws, (long)N * K, (int)R, (long)N * K, dwe, K, 1, N, st);
+// ------------------------------------------------------------------------------------------------ host side
+// atomnas_pw_gemm_nt validates its arguments into ONE NtArgs block; launch_nt is the ordered list of kernel families.  A family is a
+// pair: nt_<family>_plan is the COMPLETE accept / reject decision (switches, shapes, layouts, instance, LDS limit), pure -- it may ask
+// num_cus() and max_lds_bytes(), never the occupancy -- and leaves what it computed in the family's plan struct; nt_<family>_launch
+// sizes the grid, runs an accepted plan and cannot decline.  The *_supported queries ask the predicates the entry points use.
+template <int V> using IC = std::integral_constant<int, V>;
+
+struct NtArgs {
+  int mode; Operand A;       // prologue (PRO_*) and operand
+  const void* Wp; int ldw;   // packed weights (atomnas_pack_weights) and their row pitch
+  Epilogue ep;
+  long M; int N, K;
+  hipStream_t st;
+  bool stats;                // the epilogue takes statistics: ep.stats && ep.stat_mode != STAT_NONE
+};
+static NtArgs nt_args(int mode, const Operand& A, const void* Wp, int ldw, const Epilogue& ep, long M, int N, int K, hipStream_t st) {
+  return NtArgs{mode, A, Wp, ldw, ep, M, N, K, st, ep.stats != nullptr && ep.stat_mode != STAT_NONE};
 }
 
-// fused expand backward: supported shapes and launch
+// The run-time switches of the pointwise host code (experiment switches: 0 hands a family's shapes to the next one in launch_nt),
+// each read once per process.
+//   ATOMNAS_NT_ST, ATOMNAS_NT_SW, ATOMNAS_NT_SWG   default 1: the st / sw / swg families (ATOMNAS_NT_ST=0 also turns atomnas_project_bwd off)
+//   ATOMNAS_NT_SWG_MAXM                            default 262144: most rows the swg family takes
+//   ATOMNAS_NT_SMALL_NARROW                        default 1: the 4-channel lane tiles of k_gemm_nt_small (0: the 16-channel form)
+//   ATOMNAS_XB_STREAM                              default 1: k_expand_bwd_s for slab-major h (0: k_expand_bwd)
+struct PwEnv { int st, sw, swg; long swg_maxm; int small_narrow, xb_stream; };
+static const PwEnv& pw_env() {
+  static const PwEnv e = {
+      getenv("ATOMNAS_NT_ST") ? atoi(getenv("ATOMNAS_NT_ST")) : 1,
+      getenv("ATOMNAS_NT_SW") ? atoi(getenv("ATOMNAS_NT_SW")) : 1,
+      getenv("ATOMNAS_NT_SWG") ? atoi(getenv("ATOMNAS_NT_SWG")) : 1,
+      // measured (r04 prototype, r05 in situ): gains at 14 x 14 and 7 x 7 (M <= 50176), none at 28 x 28 (M = 200704: every stage moves
+      // 12 KB of weights from L2 for 8 KB of activations) -- until round 6 took two thirds of the prologue's instructions out (common.h: Act):
+      // since then 0.098 -> 0.077 ms at M = 200704, N = 40, K = 720 (tools/pwbench.py project), and the row limit is 262144
+      getenv("ATOMNAS_NT_SWG_MAXM") ? atol(getenv("ATOMNAS_NT_SWG_MAXM")) : 262144,
+      getenv("ATOMNAS_NT_SMALL_NARROW") ? atoi(getenv("ATOMNAS_NT_SMALL_NARROW")) : 1,
+      getenv("ATOMNAS_XB_STREAM") ? atoi(getenv("ATOMNAS_XB_STREAM")) : 1,
+  };
+  return e;
+}
+
+// Row slots of a persistent grid: one round of resident workgroups, shared by the `ngroups` channel groups a row slot spans, at most
+// one slot per row block and at most `cap` (the partial rows of the statistics or the partials of a workspace; 0: no cap), at least 1.
+template <typename KernelT>
+static long row_slots(KernelT kern, int threads, size_t lds, int ngroups, long row_blocks, long cap) {
+  long R = (long)num_cus() * resident_per_cu(kern, threads, lds) / ngroups;
+  if (R > row_blocks) R = row_blocks;
+  if (cap > 0 && R > cap) R = cap;
+  return R < 1 ? 1 : R;
+}
+static long stat_cap(const NtArgs& a) { return a.stats ? a.ep.stat_rows : 0; }   // every row slot owns one partial row
+
+// f receives the prologue mode as a compile-time constant
+template <typename F> static auto for_mode(int mode, F&& f) {
+  if (mode == PRO_NONE) return f(IC<PRO_NONE>{});
+  if (mode == PRO_BNRELU) return f(IC<PRO_BNRELU>{});
+  return f(IC<PRO_BNBWD>{});
+}
+
+// ---- sw: narrow output of a wide slab-major input (k_gemm_nt_sw: the projection forward of the early stages)
+struct NtSwPlan { int ut, nch, depth; size_t lds; };
+constexpr int SW_MAXN = 48, SW_MINK = 97, SW_MAXK = 448;
+constexpr long SW_MINM = 16384;
+#define SW_INSTANCES(X) X(1, 5) X(1, 7) X(2, 5) X(2, 7) X(3, 5) X(3, 7)   // (UT, NCH): N <= 16 UT, K <= 64 NCH
+
+static bool nt_sw_plan(const NtArgs& a, NtSwPlan& p) {
+  const Epilogue& ep = a.ep;
+  if (!pw_env().sw || a.mode != PRO_BNRELU || a.A.ss1 <= 0 || a.N > SW_MAXN || a.N % 8 != 0 || a.K > SW_MAXK || a.K < SW_MINK ||
+      a.M < SW_MINM || ep.out_f32 || ep.css != 0 || ep.add || ep.z || ep.mask || ep.bias || (a.stats && ep.stat_mode != STAT_SQ))
+    return false;
+  p.ut = (a.N + 15) / 16;
+  p.nch = (a.K + 63) / 64 <= 5 ? 5 : 7;
+  const size_t fixed = (size_t)16 * p.ut * (p.nch * 64 + 8) * sizeof(bf16_t) + (size_t)2 * p.nch * 64 * sizeof(float) +
+                       (size_t)4 * 2 * 16 * p.ut * sizeof(float);   // weights, scale / shift, statistics
+  p.depth = 2 * (fixed + 4 * 8192) + 4096 <= max_lds_bytes() ? 4 : 3;   // deepest ring that leaves room for two workgroups per CU
+  p.lds = fixed + (size_t)p.depth * 8192;
+  return 2 * p.lds + 2048 <= max_lds_bytes();
+}
+// the launch of the sw and swg kernels (same parameters): workgroups of `waves` waves own row blocks of 16 rows per wave
+template <typename KernelT>
+static int nt_sw_run(const char* what, KernelT kern, int waves, size_t lds, const NtArgs& a) {
+  const long R = row_slots(kern, waves * 64, lds, 1, (a.M + waves * 16 - 1) / (waves * 16), stat_cap(a));
+  hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(waves * 64), lds, a.st, (const bf16_t*)a.A.p1, a.A.ss1, a.A.c1, a.A.c2, a.A.relu,
+                     (const bf16_t*)a.Wp, a.ldw, (bf16_t*)a.ep.c, a.ep.ldc, a.stats ? a.ep.stats : nullptr, a.ep.stat_rows, a.M, a.N, a.K);
+  return check_launch(what);
+}
+static int nt_sw_launch(const NtSwPlan& p, const NtArgs& a) {
+#define X(UT, NCH) \
+  if (p.ut == UT && p.nch == NCH) return nt_sw_run("gemm_nt_sw", p.depth == 4 ? k_gemm_nt_sw<UT, NCH, 4> : k_gemm_nt_sw<UT, NCH, 3>, 4, p.lds, a);
+  SW_INSTANCES(X)
+#undef X
+  return 1;   // not reached: nt_sw_plan leaves ut in 1..3 and nch in {5, 7}
+}
+
+// ---- swg: the projection forward of the late stages, weights in the LDS-DMA queue (k_gemm_nt_swg)
+struct NtSwgPlan { int ut; bool wide; size_t lds; };
+constexpr int SWG_MAXN = 320, SWG_MINK = 256, SWG_DEPTH = 3;
+constexpr long SWG_MINM = 8192;   // the upper row limit is a switch: pw_env().swg_maxm
+
+static bool nt_swg_plan(const NtArgs& a, NtSwgPlan& p) {
+  const Epilogue& ep = a.ep;
+  if (!pw_env().swg || a.mode != PRO_BNRELU || a.A.ss1 <= 0 || a.N % 8 != 0 || a.N > SWG_MAXN || a.K < SWG_MINK || a.K % 4 != 0 ||
+      a.M < SWG_MINM || a.M > pw_env().swg_maxm || a.ldw < 64 || a.ldw % 8 != 0 || ep.out_f32 || ep.css != 0 || ep.add || ep.z || ep.mask ||
+      ep.bias || (a.stats && ep.stat_mode != STAT_SQ) || !a.A.c1 || !a.A.c2)
+    return false;
+  p.ut = (a.N + 15) / 16;
+  if (p.ut != 3 && p.ut != 5 && p.ut != 6 && p.ut != 12 && p.ut != 20) return false;   // the instances of nt_swg_launch
+  // 128-row stages (eight waves, one weight chunk per 128 rows: half the weight traffic per activation byte) where they still fill the
+  // chip: 14 x 14 (392 workgroups); 64-row stages at 7 x 7 (196 workgroups of four waves).
+  // wide outputs: four-wave stages only (an eight-wave instance would have 128 registers per lane for 2 x 16 UT accumulators and
+  // weight fragments: it spills, and a scratch reload inside the ring loop drains the queue -- tools/check_asm_waits.py flags it)
+  p.wide = (a.M + 127) / 128 >= num_cus() && p.ut <= 6;
+  const int nwv = p.wide ? 8 : 4;
+  p.lds = (size_t)nwv * 2 * 16 * p.ut * sizeof(float) + (size_t)SWG_DEPTH * (2 * nwv + 2 * p.ut + 1) * 1024;
+  return p.lds <= max_lds_bytes();
+}
+static int nt_swg_launch(const NtSwgPlan& p, const NtArgs& a) {
+#define X(UT, WGPC, NWV) return nt_sw_run("gemm_nt_swg", k_gemm_nt_swg<UT, SWG_DEPTH, WGPC, NWV>, NWV, p.lds, a);
+  if (p.wide) {   // ut <= 6
+    if (p.ut == 3) X(3, 1, 8)
+    if (p.ut == 5) X(5, 1, 8)
+    X(6, 1, 8)
+  }
+  if (p.ut == 3) X(3, 2, 4)
+  if (p.ut == 5) X(5, 2, 4)
+  if (p.ut == 6) X(6, 2, 4)
+  if (p.ut == 12) X(12, 1, 4)
+  X(20, 1, 4)
+#undef X
+}
+
+// ---- st: column-stationary streaming form, the output is the wide operand (k_gemm_nt_st)
+struct NtStPlan { int kind, ksteps; };   // ST_FWD / ST_MASK; k-steps of the instance: 1, 2, 3 or 6
+constexpr int ST_MAXK = 192, ST_MINN = 96;
+constexpr long ST_MINM = 1024;
+
+// The layouts and epilogues the streaming instances are written for (see k_gemm_nt_st): 0, ST_FWD or ST_MASK.  atomnas_project_bwd
+// asks this alone (its shapes: atomnas_project_bwd_supported); nt_st_plan puts the shape gate of gemm_nt in front of it.
+static int nt_st_kind(const NtArgs& a) {
+  const Operand& A = a.A;
+  const Epilogue& ep = a.ep;
+  const long M = a.M, N = a.N, K = a.K;
+  if (!pw_env().st || a.mode != PRO_NONE || (K & 7) || ep.bias || ep.add || ep.out_f32) return 0;
+  if (ep.stats != nullptr && ep.stat_mode == STAT_NONE) return 0;
+  // a row range is at most 4096 tiles (32-bit tile offsets) and owns one partial row of the statistics
+  if (a.stats && ((M + 15) / 16 + ep.stat_rows - 1) / ep.stat_rows > 4096) return 0;
+  // 32-bit byte offsets below 2^31 inside the per-wave resources: the whole A tensor, four slabs (one chunk) of C and z
+  const long a_bytes = A.ss1 ? ((long)((K + 15) / 16 - 1) * A.ss1 + M * 16) * 2 : M * (long)A.ld1 * 2;
+  if (a_bytes >= (1L << 31)) return 0;
+  if (ep.css ? (3 * ep.css + M * 16) * 2 >= (1L << 31) : ((N & 7) || (long)ep.ldc * 2 * 16 * 4096 >= (1L << 31))) return 0;
+  if (!ep.z) return (!a.stats || ep.stat_mode == STAT_SQ) ? ST_FWD : 0;
+  if (!ep.mask || (a.stats && ep.stat_mode != STAT_Z)) return 0;
+  if (ep.zss ? (3 * ep.zss + M * 16) * 2 >= (1L << 31) : ((N & 7) || (long)ep.ldz * 2 * 16 * 4096 >= (1L << 31))) return 0;
+  return ST_MASK;
+}
+// anything else in this shape class (a prologue, a bias / residual epilogue, K not a multiple of 8) takes the kernels further down
+static bool nt_st_plan(const NtArgs& a, NtStPlan& p) {
+  if (a.K > ST_MAXK || a.N < 2 * a.K || a.N < ST_MINN || a.M < ST_MINM) return false;
+  const int ks = (a.K + 31) / 32;
+  p.ksteps = ks <= 3 ? ks : 6;
+  p.kind = nt_st_kind(a);
+  return p.kind != 0;
+}
+// Work items of k_gemm_nt_st: row ranges of tiles_per_item 16-row tiles x 64-channel chunks, one wave each (`wchunks` wave slots per
+// range, `waves` resident waves).  At least 8 tiles and min_tpi (every range owns one partial row of the statistics), and no more
+// ranges than one round of workgroups holds or than max_parts (partials of a workspace; 0: no such limit).
+static long st_tiles_per_item(long mtiles, long wchunks, long waves, long min_tpi, long max_parts) {
+  long tpi = (mtiles * wchunks + waves - 1) / waves;
+  if (tpi < 8) tpi = 8;
+  if (tpi < min_tpi) tpi = min_tpi;
+  long max_ranges = waves / wchunks > 0 ? waves / wchunks : 1;
+  if (max_parts > 0 && max_ranges > max_parts) max_ranges = max_parts;
+  if ((mtiles + tpi - 1) / tpi > max_ranges) tpi = (mtiles + max_ranges - 1) / max_ranges;
+  return tpi;
+}
+template <int KSTEPS, int EPK, bool SH, int BT>
+static int nt_st_launch_as(const NtArgs& a) {
+  using Cfg = StCfg<KSTEPS, EPK>;
+  const Epilogue& ep = a.ep;
+  const int nchunks = (a.N + 63) / 64;
+  const long mtiles = (a.M + 15) / 16;
+  const long min_tpi = ep.stats ? (mtiles + ep.stat_rows - 1) / ep.stat_rows : 1;   // every row range owns one partial row
+  auto kern = k_gemm_nt_st<KSTEPS, EPK, Cfg::PD, BT, Cfg::WPE, 0, SH>;
+  const size_t lds = (size_t)(SH ? 2 : 4) * BT * KSTEPS * 1024 +   // burst staging (+ z coefficients)
+                     (EPK == ST_FWD ? 0 : (size_t)4 * (16 + 64) * PB_RP * sizeof(bf16_t) + 4 * 128 * sizeof(float));
+  const long waves = (long)num_cus() * resident_per_cu(kern, 256, lds) * 4;
+  const long wchunks = SH ? (long)((nchunks + 3) / 4) * 4 : nchunks;   // wave slots per row range
+  long tiles_per_item = st_tiles_per_item(mtiles, wchunks, waves, min_tpi, 0);
+  if (tiles_per_item > 4096) tiles_per_item = 4096;   // keeps t * tile bytes in 32 bits (nt_st_kind)
+  const long nrg = (mtiles + tiles_per_item - 1) / tiles_per_item;
+  const long blocks = SH ? nrg * ((nchunks + 3) / 4) : (nrg * nchunks + 3) / 4;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, a.st, a.A, (const bf16_t*)a.Wp, a.ldw, ep, a.M, a.N, a.K, nchunks,
+                     (int)tiles_per_item, (float*)nullptr);
+  return check_launch("gemm_nt_st");
+}
+static int nt_st_launch(const NtStPlan& p, const NtArgs& a) {
+  auto go = [&](auto ks, auto epk) {
+    constexpr int KSTEPS = decltype(ks)::value, EPK = decltype(epk)::value;
+    using Cfg = StCfg<KSTEPS, EPK>;
+    // Bursts shared by the four waves of a workgroup (one read of the narrow operand per workgroup instead of per wave) where whole
+    // groups of four chunks waste at most 5 % of the wave slots: 14x14 (23 / 27 chunks) -10..-18 %, 28x28 (12) equal; with 5 or 7 chunks
+    // the repeated chunk costs more than the sharing saves (112x112 +38 %, 56x56 masked form +15 %; r03, tools/pwbench.py).
+    const int nchunks = (a.N + 63) / 64;
+    if (Cfg::SH && ((nchunks + 3) / 4 * 4 - nchunks) * 20 <= nchunks) return nt_st_launch_as<KSTEPS, EPK, Cfg::SH, Cfg::BT>(a);
+    return nt_st_launch_as<KSTEPS, EPK, false, Cfg::BTP>(a);
+  };
+  auto kind = [&](auto ks) { return p.kind == ST_FWD ? go(ks, IC<ST_FWD>{}) : go(ks, IC<ST_MASK>{}); };
+  return p.ksteps == 1 ? kind(IC<1>{}) : p.ksteps == 2 ? kind(IC<2>{}) : p.ksteps == 3 ? kind(IC<3>{}) : kind(IC<6>{});
+}
+
+// ---- small: the stem and the first block, both sides narrow (k_gemm_nt_small)
+struct NtSmallPlan { int kst, ntile; };   // k-steps (1, 2); column tiles of a lane's 4 channels (1, 2, 4), 0: the 16-channel form
+constexpr int SMALL_MAXN = 64, SMALL_MAXK = 64;
+constexpr long SMALL_MINM = 65536;
+
+static bool nt_small_plan(const NtArgs& a, NtSmallPlan& p) {
+  if (a.N > SMALL_MAXN || a.K > SMALL_MAXK || a.M < SMALL_MINM) return false;
+  p.kst = a.K <= 32 ? 1 : 2;
+  // lanes own 4 channels x NT tiles where the output allows it (bf16, N a multiple of 4)
+  p.ntile = (pw_env().small_narrow && !a.ep.out_f32 && a.N % 4 == 0) ? (a.N <= 16 ? 1 : a.N <= 32 ? 2 : 4) : 0;
+  return true;
+}
+static int nt_small_launch(const NtSmallPlan& p, const NtArgs& a) {
+  auto go = [&](auto mode, auto kst) {
+    constexpr int MODE = decltype(mode)::value, KST = decltype(kst)::value;
+    auto kern = p.ntile == 1 ? k_gemm_nt_small<MODE, KST, 1> : p.ntile == 2 ? k_gemm_nt_small<MODE, KST, 2>
+              : p.ntile == 4 ? k_gemm_nt_small<MODE, KST, 4> : k_gemm_nt_small<MODE, KST, 0>;
+    const size_t lds = a.stats ? (size_t)8 * 64 * sizeof(float) : 0;
+    const long R = row_slots(kern, 256, lds, 1, (a.M + 63) / 64, stat_cap(a));
+    hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(256), lds, a.st, a.A, (const bf16_t*)a.Wp, a.ldw, a.ep, a.M, a.N, a.K);
+  };
+  for_mode(a.mode, [&](auto mode) { p.kst == 1 ? go(mode, IC<1>{}) : go(mode, IC<2>{}); });
+  return check_launch("gemm_nt_small");
+}
+
+// ---- ws: weights of a 64 / 128-channel group in LDS (k_gemm_nt_ws)
+struct NtWsPlan { int ncg, rt; };   // 64-channel chunks per workgroup; 16-row subtiles per wave
+constexpr int WS_MINK = 97;
+constexpr long WS_MINM = 4096;
+// two 16-row subtiles per wave (each weight fragment read feeds two MFMAs) when there are enough 128-row blocks:
+// measured in situ per shape (bs 256 step, same box): one subtile per wave is faster wherever the prologue is
+// BN-apply (the projection forward: M = 50176 -28 %, 200704 -15 %, 802816 -7 % -- the two-subtile BNRELU instance with two chunks
+// needs 335 registers, one wave per SIMD) and on the small maps; two subtiles only pay with the two-stream BN-backward prologue
+// on the large maps (M = 200704: -3 %)
+constexpr long WS_RT2_MINM = 100000;
+
+static bool nt_ws_plan(const NtArgs& a, NtWsPlan& p) {
+  if (a.K < WS_MINK || a.M < WS_MINM) return false;
+  p.ncg = a.N > 64 ? 2 : 1;
+  p.rt = (a.mode == PRO_BNBWD && a.M >= WS_RT2_MINM) ? 2 : 1;
+  return true;
+}
+template <int MODE, int NCG, int RT>
+static void nt_ws_launch_as(const NtArgs& a) {
+  auto kern = k_gemm_nt_ws<MODE, NCG, RT>;
+  const int ngroups = (a.N + 64 * NCG - 1) / (64 * NCG);
+  const size_t lds = (size_t)2 * 64 * NCG * WS_WP * sizeof(bf16_t) + 2 * 3 * WS_KC * sizeof(float) +
+                     (a.stats ? (size_t)8 * 64 * NCG * sizeof(float) : 0);
+  const long R = row_slots(kern, 256, lds, ngroups, (a.M + 64 * RT - 1) / (64 * RT), stat_cap(a));
+  const int wrows = (a.N + 63) / 64 * 64;   // rows of the packed weight matrix
+  hipLaunchKernelGGL(kern, dim3((unsigned)(R * ngroups)), dim3(256), lds, a.st, a.A, (const bf16_t*)a.Wp, a.ldw, wrows, a.ep, a.M, a.N, a.K);
+}
+static int nt_ws_launch(const NtWsPlan& p, const NtArgs& a) {
+  for_mode(a.mode, [&](auto mode) {
+    constexpr int MODE = decltype(mode)::value;
+    if constexpr (MODE == PRO_BNBWD) {   // the only prologue nt_ws_plan gives two subtiles
+      if (p.rt == 2) return p.ncg == 2 ? nt_ws_launch_as<MODE, 2, 2>(a) : nt_ws_launch_as<MODE, 1, 2>(a);
+    }
+    return p.ncg == 2 ? nt_ws_launch_as<MODE, 2, 1>(a) : nt_ws_launch_as<MODE, 1, 1>(a);
+  });
+  return check_launch("gemm_nt_ws");
+}
+
+// ---- generic: every shape, both storage types (k_gemm_nt)
+struct NtGenericPlan { int ncg; };   // two 64-channel chunks stay live when there is more than one
+static bool nt_generic_plan(const NtArgs& a, NtGenericPlan& p) {
+  p.ncg = a.N > 64 ? 2 : 1;
+  return true;
+}
+template <typename T>
+static int nt_generic_launch(const NtGenericPlan& p, const NtArgs& a) {
+  constexpr int KS = 4 * Mma<T>::EPL;
+  const int Kpad = (a.K + KS - 1) / KS * KS;
+  auto go = [&](auto mode, auto ncg) {
+    constexpr int NCG = decltype(ncg)::value;
+    auto kern = k_gemm_nt<T, decltype(mode)::value, NCG>;
+    const int ngroups = (a.N + 64 * NCG - 1) / (64 * NCG);
+    const size_t lds = a.stats ? (size_t)8 * 64 * NCG * sizeof(float) : 0;
+    // persistent grid-stride loop over (row tile, channel group) items: row slots of 4 tiles
+    const long R = row_slots(kern, 256, lds, ngroups, (a.M + 63) / 64, stat_cap(a));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(R * ngroups)), dim3(256), lds, a.st, a.A, (const T*)a.Wp, a.ldw, a.ep, a.M, a.N, a.K, Kpad);
+  };
+  for_mode(a.mode, [&](auto mode) { p.ncg == 2 ? go(mode, IC<2>{}) : go(mode, IC<1>{}); });
+  return check_launch("gemm_nt");
+}
+
+// The dispatch of atomnas_pw_gemm_nt: the first family that accepts runs.
+template <typename T>
+static int launch_nt(const NtArgs& a) {
+  if constexpr (sizeof(T) == 2) {
+    NtSwPlan sw;
+    if (nt_sw_plan(a, sw)) return nt_sw_launch(sw, a);
+    NtSwgPlan swg;
+    if (nt_swg_plan(a, swg)) return nt_swg_launch(swg, a);
+    NtStPlan st;
+    if (nt_st_plan(a, st)) return nt_st_launch(st, a);
+    NtSmallPlan small;
+    if (nt_small_plan(a, small)) return nt_small_launch(small, a);
+    NtWsPlan ws;
+    if (nt_ws_plan(a, ws)) return nt_ws_launch(ws, a);
+  }
+  NtGenericPlan g;
+  nt_generic_plan(a, g);
+  return nt_generic_launch<T>(g, a);
+}
+
+// ---- fused projection backward (the streaming form with the weight gradient: A is the materialised dP, no prologue)
+// the gemm_nt that atomnas_project_bwd is: gh[M, hid] = mask_z(dP[M, oup] x Wp^T) with the [sum gh, sum gh*z] statistics
+static NtArgs project_bwd_args(const void* g, int ldg, const void* wpt, int ldw, const void* z, int ldz, long z_ss, const float* zscale,
+                               const float* zshift, int act, void* gh, int ldgh, long gh_ss, float* stats, int stat_rows, long M, int oup,
+                               int hid, hipStream_t st) {
+  const Operand A{g, ldg, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, 0};
+  const Epilogue ep{gh, ldgh, 0, nullptr, 0, z, ldz, gh_ss, z_ss, zscale, zshift, act, nullptr, stats, STAT_Z, stat_rows};
+  return nt_args(PRO_NONE, A, wpt, ldw, ep, M, hid, oup, st);
+}
+template <int KSTEPS, int UT>
+static int launch_project_bwd_st(const NtArgs& a, float* dwp, long si, long sj, float* ws, long ws_floats) {
+  using Cfg = StCfg<KSTEPS, ST_PBWD>;
+  const long M = a.M;
+  const int N = a.N, K = a.K;
+  const int nchunks = (N + 63) / 64;
+  const long mtiles = (M + 15) / 16;
+  auto kern = k_gemm_nt_st<KSTEPS, ST_PBWD, Cfg::PD, Cfg::BT, Cfg::WPE, UT, false>;
+  const size_t lds = (size_t)4 * Cfg::BT * KSTEPS * 1024 + (size_t)4 * (16 * UT + 64) * PB_RP * sizeof(bf16_t) + 4 * 128 * sizeof(float);
+  const long waves = (long)num_cus() * resident_per_cu(kern, 256, lds) * 4;
+  const long max_parts = ws_floats / ((long)K * N);   // every row range owns one partial of the weight gradient
+  ATOMNAS_REQUIRE(max_parts >= 1, "project_bwd: workspace too small for one partial (%ld floats)", (long)K * N);
+  const long tiles_per_item = st_tiles_per_item(mtiles, nchunks, waves, (mtiles + a.ep.stat_rows - 1) / a.ep.stat_rows, max_parts);
+  ATOMNAS_REQUIRE(tiles_per_item <= 4096, "project_bwd: %ld row tiles per work item (workspace / statistics rows too small for M=%ld)", tiles_per_item, M);
+  const long nranges = (mtiles + tiles_per_item - 1) / tiles_per_item;
+  const long items = nranges * nchunks;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((items + 3) / 4)), dim3(256), lds, a.st, a.A, (const bf16_t*)a.Wp, a.ldw, a.ep, M, N, K, nchunks,
+                     (int)tiles_per_item, ws);
+  if (int rc = check_launch("project_bwd_st")) return rc;
+  return reduce_parts(ws, (long)K * N, (int)nranges, (long)K * N, dwp, N, si, sj, a.st);
+}
+
+// ---- fused expand backward: one instance table for the query and both kernels
+// (UT, NCH): inp <= 16 UT input channels, hid <= 64 NCH hidden channels.  The weight-gradient accumulators (4 registers per
+// (16 input channels, 64 hidden channels) tile) must leave room for two workgroups per CU: 4 UT NCH <= XB_MINB2_LIMIT.
+#define XB_INSTANCES(X) X(1, 5) X(1, 7) X(1, 12) X(2, 5) X(2, 7) X(3, 5)
 static inline int xb_nch(int HT) {
   const int n = (HT + WS_KC - 1) / WS_KC;
   return n <= 5 ? 5 : (n <= 7 ? 7 : (n <= 12 ? 12 : 0));
 }
+static bool xb_has_instance(int inp, int hid) {
+  const int ut = (inp + 15) / 16, nch = xb_nch(hid);
+#define X(UTV, NCHV) if (ut == UTV && nch == NCHV) return true;
+  XB_INSTANCES(X)
+#undef X
+  return false;
+}
+struct XbArgs {   // atomnas_expand_bwd's arguments after validation: W is We^T packed, vb is null without mpk, N = inp, K = hid
+  const bf16_t* h; int ldh; long hss; const float* c1;
+  const bf16_t* x; int ldx; const bf16_t* W; int ldw; const bf16_t* add; int ldadd; bf16_t* gx; int ldgx;
+  const bf16_t* mpk; int ldm; const float* vb;
+  float *dwe, *ws; long ws_floats; long M; int N, K; hipStream_t st;
+};
+// Grid of both kernels: one round of resident workgroups over the 64-row blocks, every workgroup owning one partial of the weight
+// gradient in the workspace.  Launches kern(R) through `launch` and sums the partials in workgroup order: dWe[n * inp + k] += R[k][n].
+template <typename KernelT, typename L>
+static int xb_run(const char* what, const XbArgs& a, KernelT kern, size_t lds, L&& launch) {
+  const long max_parts = a.ws_floats / ((long)a.N * a.K);
+  ATOMNAS_REQUIRE(max_parts >= 1, "expand_bwd: workspace too small for one partial (%ld floats)", (long)a.N * a.K);
+  const long R = row_slots(kern, 256, lds, 1, (a.M + 63) / 64, max_parts);
+  launch((unsigned)R);
+  if (int rc = check_launch(what)) return rc;
+  return reduce_parts(a.ws, (long)a.N * a.K, (int)R, (long)a.N * a.K, a.dwe, a.K, 1, a.N, a.st);
+}
+
+// the streaming kernel (k_expand_bwd_s): slab-major h of at least three 64-channel chunks
+struct XbStreamPlan { int depth; size_t lds; };
+static bool xb_stream_plan(const XbArgs& a, XbStreamPlan& p) {
+  if (!pw_env().xb_stream || a.hss <= 0 || a.M < 64 || a.ldx < 8 || (a.add && a.ldadd < 8)) return false;
+  // The x / residual tiles are double-buffered per row block: the copy for block b + 2 is issued DEPTH - 1 stages ahead of that block's
+  // first stage, which lies inside block b + 1 only if a block has at least DEPTH - 1 = 3 stages.  Narrower hidden tensors (K <= 128:
+  // one or two 64-channel chunks) take k_expand_bwd.
+  if ((a.K + 63) / 64 < 3) return false;
+  const int ut = (a.N + 15) / 16, nch = xb_nch(a.K);
+  const size_t fixed = (size_t)16 * ut * (nch * 64 + 8) * sizeof(bf16_t) + (size_t)4 * 2 * ut * 1024;   // weights + x and residual tiles
+  p.depth = 2 * (fixed + 4 * 8192) + 4096 <= max_lds_bytes() ? 4 : 3;   // deepest ring that leaves room for two workgroups per CU
+  p.lds = fixed + (size_t)p.depth * 8192;
+  return p.lds <= max_lds_bytes();
+}
 template <int UT, int NCH>
-static int launch_expand_bwd_cfg(const Operand& A, const bf16_t* W, int ldw, int wrows, const bf16_t* x, int ldx, const Epilogue& ep, float* dwe,
-                                 float* ws, long ws_floats, long M, int N, int K, const bf16_t* mpk, int ldm, hipStream_t st) {
+static int xb_stream_launch(const XbStreamPlan& p, const XbArgs& a) {
+  static_assert(4 * UT * NCH <= XB_MINB2_LIMIT, "expand backward instance with too many accumulator registers");
+  auto kern = p.depth == 4 ? k_expand_bwd_s<UT, NCH, 4> : k_expand_bwd_s<UT, NCH, 3>;
+  return xb_run("expand_bwd(stream)", a, kern, p.lds, [&](unsigned R) {
+    hipLaunchKernelGGL(kern, dim3(R), dim3(256), p.lds, a.st, a.h, a.hss, a.c1, a.W, a.ldw, a.x, a.ldx, a.add, a.ldadd, a.gx, a.ldgx, a.mpk,
+                       a.ldm, a.vb, a.ws, a.M, a.N, a.K);
+  });
+}
+// the register-prefetch kernel (k_expand_bwd): every layout
+template <int UT, int NCH>
+static int xb_launch(const XbArgs& a) {
+  static_assert(4 * UT * NCH <= XB_MINB2_LIMIT, "expand backward instance with too many accumulator registers");
   auto kern = k_expand_bwd<UT, NCH>;
   const size_t lds = (size_t)2 * 64 * WS_WP * sizeof(bf16_t) + 2 * 3 * WS_KC * sizeof(float) + (size_t)2 * 64 * XB_DP * sizeof(bf16_t) +
                      (size_t)16 * UT * XB_DP * sizeof(bf16_t);
-  const long rblocks = (M + 63) / 64;
-  long R = (long)num_cus() * resident_per_cu(kern, 256, lds);   // one round of resident workgroups
-  if (R > rblocks) R = rblocks;
-  const long max_parts = ws_floats / ((long)N * K);   // every workgroup owns one partial of the weight gradient
-  if (R > max_parts) R = max_parts;
-  ATOMNAS_REQUIRE(R >= 1, "expand_bwd: workspace too small for one partial (%ld floats)", (long)N * K);
-  hipLaunchKernelGGL(kern, dim3((unsigned)R), dim3(256), lds, st, A, W, ldw, wrows, x, ldx, ep, ws, M, N, K, mpk, ldm);
-  if (int rc = check_launch("expand_bwd")) return rc;
-  // dWe[n * inp + k] += sum over workgroups of R[k][n], in workgroup order
-  return reduce_parts(ws, (long)N * K, (int)R, (long)N * K, dwe, K, 1, N, st);
+  // the kernel stages three coefficient vectors per chunk; only the first is used
+  const Operand A{a.h, a.ldh, nullptr, 0, a.hss, 0, a.c1, a.c1, a.c1, 0};
+  const Epilogue ep{a.gx, a.ldgx, 0, a.add, a.ldadd, nullptr, 0, 0, 0, nullptr, nullptr, 0, a.vb, nullptr, STAT_NONE, 0};
+  const int wrows = (a.N + 63) / 64 * 64;
+  return xb_run("expand_bwd", a, kern, lds, [&](unsigned R) {
+    hipLaunchKernelGGL(kern, dim3(R), dim3(256), lds, a.st, A, a.W, a.ldw, wrows, a.x, a.ldx, ep, a.ws, a.M, a.N, a.K, a.mpk, a.ldm);
+  });
+}
+static int launch_expand_bwd(const XbArgs& a) {
+  const int ut = (a.N + 15) / 16, nch = xb_nch(a.K);
+  XbStreamPlan sp;
+  const bool stream = xb_stream_plan(a, sp);
+#define X(UTV, NCHV) if (ut == UTV && nch == NCHV) return stream ? xb_stream_launch<UTV, NCHV>(sp, a) : xb_launch<UTV, NCHV>(a);
+  XB_INSTANCES(X)
+#undef X
+  set_error("expand_bwd: no instance for inp=%d hid=%d", a.N, a.K);
+  return 1;
 }
 
 }  // namespace atomnas
@@ -2330,21 +2416,18 @@ extern "C" int atomnas_pw_gemm_nt(int a_mode, const void* a, int lda, long a_ss,
   ATOMNAS_REQUIRE(!z || z_ss >= M * 16 || (z_ss == 0 && ldz >= N && ldz % 8 == 0), "pw_gemm_nt: bad z pitch");
   ATOMNAS_REQUIRE(!mask || (z && zscale && zshift), "pw_gemm_nt: mask needs z, zscale, zshift");
   ATOMNAS_REQUIRE(stat_mode != STAT_Z || z, "pw_gemm_nt: STAT_Z needs z");
-  Operand A{a, lda, a2, lda2, a_ss, a2_ss, ac1, ac2, ac3, a_relu};
+  const Operand A{a, lda, a2, lda2, a_ss, a2_ss, ac1, ac2, ac3, a_relu};
   if (check_operand("pw_gemm_nt", A, a_mode, K)) return 1;
-  Epilogue ep{c, ldc, out_f32, add, ldadd, z, ldz, c_ss, z_ss, zscale, zshift, mask, bias, stats, stat_mode, stat_rows};
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_F32) return launch_nt<float>(a_mode, A, wp, ldw, ep, M, N, K, st);
-  return launch_nt<bf16_t>(a_mode, A, wp, ldw, ep, M, N, K, st);
+  const Epilogue ep{c, ldc, out_f32, add, ldadd, z, ldz, c_ss, z_ss, zscale, zshift, mask, bias, stats, stat_mode, stat_rows};
+  const NtArgs args = nt_args(a_mode, A, wp, ldw, ep, M, N, K, (hipStream_t)stream);
+  return dtype == DT_F32 ? launch_nt<float>(args) : launch_nt<bf16_t>(args);
 }
 
-// 1 when atomnas_expand_bwd has an instance for this shape: bf16 storage, and the weight-gradient accumulators (4 registers per
-// (16 input channels, 64 hidden channels) tile) leave room for two workgroups per CU.  Measured in situ (bs 256): 24 -> 432 and
-// 16 -> 288 run 1.7x / 1.4x faster than the two GEMMs; 40 -> 720 (144 accumulator registers, one workgroup per CU, spills) was
-// 1.7x SLOWER and has no instance.
+// 1 when atomnas_expand_bwd has an instance for this shape: bf16 storage and an entry of XB_INSTANCES.  Measured in situ (bs 256):
+// 24 -> 432 and 16 -> 288 run 1.7x / 1.4x faster than the two GEMMs; 40 -> 720 (144 accumulator registers, one workgroup per CU,
+// spills) was 1.7x SLOWER and has no instance.
 extern "C" int atomnas_expand_bwd_supported(int inp, int hid, int dtype) {
-  if (dtype != DT_BF16 || inp < 1 || inp > 48 || hid < 1 || xb_nch(hid) == 0) return 0;
-  return 4 * ((inp + 15) / 16) * xb_nch(hid) <= XB_MINB2_LIMIT;
+  return dtype == DT_BF16 && inp >= 1 && hid >= 1 && xb_has_instance(inp, hid);
 }
 
 // Backward of the expand convolution (models/mobilenet_base.py:316-320) without its raw output E, both gradients from ONE pass over h:
@@ -2359,32 +2442,9 @@ extern "C" int atomnas_expand_bwd(const void* h, int ldh, long h_ss, const float
   ATOMNAS_REQUIRE(!mp || (ldm >= (inp + 31) / 32 * 32 && ldm % 8 == 0), "expand_bwd: bad pitch of the x M term (ldm=%d)", ldm);
   ATOMNAS_REQUIRE(ldx >= inp && ldx % 8 == 0 && ldgx >= inp && ldgx % 8 == 0 && (!add || (ldadd >= inp && ldadd % 8 == 0)), "expand_bwd: bad pitch");
   ATOMNAS_REQUIRE(ldw >= (hid + 31) / 32 * 32 && ldw % 8 == 0, "expand_bwd: packed weight pitch %d too small for hid=%d", ldw, hid);
-  const float *c2 = c1, *c3 = c1;   // the register-prefetch kernel stages three coefficient vectors per chunk; only the first is used
-  Operand A{h, ldh, nullptr, 0, h_ss, 0, c1, c2, c3, 0};
-  Epilogue ep{gx, ldgx, 0, add, ldadd, nullptr, 0, 0, 0, nullptr, nullptr, 0, mp ? vb : nullptr, nullptr, STAT_NONE, 0};
-  hipStream_t st = (hipStream_t)stream;
-  const int ut = (inp + 15) / 16, nch = xb_nch(hid);
-  const bf16_t* W = (const bf16_t*)wt;
-  const bf16_t* X = (const bf16_t*)x;
-  const int wrows = (inp + 63) / 64 * 64;
-  // slab-major h: the streaming kernel (ATOMNAS_XB_STREAM=0: experiment switch back to k_expand_bwd)
-  static const int xs_on = getenv("ATOMNAS_XB_STREAM") ? atoi(getenv("ATOMNAS_XB_STREAM")) : 1;
-  if (xs_on && h_ss > 0 && M >= 64 && ldx >= 8 && (!add || ldadd >= 8)) {
-#define XS_CASE(UTV, NCHV)                                                                                                             \
-  if (ut == UTV && nch == NCHV) {                                                                                                      \
-    const int rc = launch_expand_bwd_s<UTV, NCHV>((const bf16_t*)h, h_ss, c1, W, ldw, X, ldx, (const bf16_t*)add, ldadd, (bf16_t*)gx, ldgx, \
-                                                  (const bf16_t*)mp, ldm, mp ? vb : nullptr, dwe, ws, ws_floats, M, inp, hid, st);     \
-    if (rc >= 0) return rc;                                                                                                            \
-  }
-    XS_CASE(1, 5) XS_CASE(1, 7) XS_CASE(1, 12) XS_CASE(2, 5) XS_CASE(2, 7) XS_CASE(3, 5)
-#undef XS_CASE
-  }
-#define XB_CASE(UTV, NCHV) \
-  if (ut == UTV && nch == NCHV) return launch_expand_bwd_cfg<UTV, NCHV>(A, W, ldw, wrows, X, ldx, ep, dwe, ws, ws_floats, M, inp, hid, (const bf16_t*)mp, ldm, st);
-  XB_CASE(1, 5) XB_CASE(1, 7) XB_CASE(1, 12) XB_CASE(2, 5) XB_CASE(2, 7) XB_CASE(3, 5)
-#undef XB_CASE
-  set_error("expand_bwd: no instance for inp=%d hid=%d", inp, hid);
-  return 1;
+  return launch_expand_bwd(XbArgs{(const bf16_t*)h, ldh, h_ss, c1, (const bf16_t*)x, ldx, (const bf16_t*)wt, ldw, (const bf16_t*)add, ldadd,
+                                  (bf16_t*)gx, ldgx, (const bf16_t*)mp, ldm, mp ? vb : nullptr, dwe, ws, ws_floats, M, inp, hid,
+                                  (hipStream_t)stream});
 }
 
 // 1 when atomnas_project_bwd has an instance for this shape: bf16 storage, oup a multiple of 8 and <= 64 (one to four 16-channel
@@ -2398,10 +2458,9 @@ extern "C" int atomnas_project_bwd_supported(int oup, int hid, int dtype) {
 extern "C" int atomnas_project_bwd_dp_supported(long M, int oup, int hid, int ldg, int ldz, long z_ss, int ldgh, long gh_ss, int stat_rows,
                                                 int dtype) {
   if (!atomnas_project_bwd_supported(oup, hid, dtype) || M <= 0 || stat_rows <= 0) return 0;
-  static float dummy;
-  Operand A{&dummy, ldg, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, 0};
-  Epilogue ep{&dummy, ldgh, 0, nullptr, 0, &dummy, ldz, gh_ss, z_ss, nullptr, nullptr, ACT_RELU, nullptr, &dummy, STAT_Z, stat_rows};
-  return nt_st_kind(PRO_NONE, A, ep, M, hid, oup) == ST_MASK ? 1 : 0;
+  static float dummy;   // stands for every pointer: the predicate asks only which are given
+  return nt_st_kind(project_bwd_args(&dummy, ldg, &dummy, 0, &dummy, ldz, z_ss, nullptr, nullptr, ACT_RELU, &dummy, ldgh, gh_ss, &dummy,
+                                     stat_rows, M, oup, hid, nullptr)) == ST_MASK;
 }
 
 // Backward of the linear projection nn.Conv2d(hid, oup, 1) (models/mobilenet_base.py:338) in ONE pass over the raw depthwise output:
@@ -2421,14 +2480,12 @@ extern "C" int atomnas_project_bwd(const void* g, int ldg, const void* wpt, int 
   ATOMNAS_REQUIRE((z_ss >= M * 16 || (z_ss == 0 && ldz >= hid && ldz % 8 == 0)) && (gh_ss >= M * 16 || (gh_ss == 0 && ldgh >= hid && ldgh % 8 == 0)),
                   "project_bwd: bad hidden layout");
   ATOMNAS_REQUIRE(ldw >= (oup + 31) / 32 * 32 && ldw % 8 == 0, "project_bwd: packed weight pitch %d too small for oup=%d", ldw, oup);
-  Operand A{g, ldg, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, 0};
-  Epilogue ep{gh, ldgh, 0, nullptr, 0, z, ldz, gh_ss, z_ss, zscale, zshift, act, nullptr, stats, STAT_Z, stat_rows};
-  hipStream_t st = (hipStream_t)stream;
-  const bf16_t* W = (const bf16_t*)wpt;
+  const NtArgs a = project_bwd_args(g, ldg, wpt, ldw, z, ldz, z_ss, zscale, zshift, act, gh, ldgh, gh_ss, stats, stat_rows, M, oup, hid,
+                                    (hipStream_t)stream);
+  ATOMNAS_REQUIRE(nt_st_kind(a) == ST_MASK, "project_bwd: needs slab-major hidden tensors (or plain ones with hid %% 8 == 0) below 2 GB per 64-channel chunk (ask atomnas_project_bwd_dp_supported)");
   const int ut = (oup + 15) / 16;
-  ATOMNAS_REQUIRE(nt_st_kind(PRO_NONE, A, ep, M, hid, oup) == ST_MASK, "project_bwd: needs slab-major hidden tensors (or plain ones with hid %% 8 == 0) below 2 GB per 64-channel chunk (ask atomnas_project_bwd_dp_supported)");
-  if (ut == 1) return launch_project_bwd_st<1, 1>(A, W, ldw, ep, dwp, si, sj, ws, ws_floats, M, hid, oup, st);
-  if (ut == 2) return launch_project_bwd_st<1, 2>(A, W, ldw, ep, dwp, si, sj, ws, ws_floats, M, hid, oup, st);
-  if (ut == 3) return launch_project_bwd_st<2, 3>(A, W, ldw, ep, dwp, si, sj, ws, ws_floats, M, hid, oup, st);
-  return launch_project_bwd_st<2, 4>(A, W, ldw, ep, dwp, si, sj, ws, ws_floats, M, hid, oup, st);
+  if (ut == 1) return launch_project_bwd_st<1, 1>(a, dwp, si, sj, ws, ws_floats);
+  if (ut == 2) return launch_project_bwd_st<1, 2>(a, dwp, si, sj, ws, ws_floats);
+  if (ut == 3) return launch_project_bwd_st<2, 3>(a, dwp, si, sj, ws, ws_floats);
+  return launch_project_bwd_st<2, 4>(a, dwp, si, sj, ws, ws_floats);
 }
