@@ -263,6 +263,8 @@ __device__ __forceinline__ void nt_flush_stats(const Epilogue& ep, const float* 
 
 struct TrFrag { bf16x4 lo, hi; };   // the two halves (k = 8 q .. + 3, + 4 .. + 7) of a transposing-read MFMA fragment
 
+template <int V> using IC = std::integral_constant<int, V>;   // a compile-time constant handed to a generic lambda (host-side fan-outs)
+
 static inline int check_operand(const char* who, const Operand& o, int mode, int C) {
   ATOMNAS_REQUIRE(o.p1 != nullptr && (o.ss1 > 0 || (o.ld1 >= C && o.ld1 % 8 == 0)), "%s: bad main stream (ld=%d, C=%d)", who, o.ld1, C);
   if (mode == PRO_BNRELU) ATOMNAS_REQUIRE(o.c1 && o.c2, "%s: BNRELU prologue needs scale and shift", who);

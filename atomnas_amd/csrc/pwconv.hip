@@ -1957,8 +1957,6 @@ __global__ __launch_bounds__(256, 2) void k_expand_bwd_s(const bf16_t* __restric
 // pair: nt_<family>_plan is the COMPLETE accept / reject decision (switches, shapes, layouts, instance, LDS limit), pure -- it may ask
 // num_cus() and max_lds_bytes(), never the occupancy -- and leaves what it computed in the family's plan struct; nt_<family>_launch
 // sizes the grid, runs an accepted plan and cannot decline.  The *_supported queries ask the predicates the entry points use.
-template <int V> using IC = std::integral_constant<int, V>;
-
 struct NtArgs {
   int mode; Operand A;       // prologue (PRO_*) and operand
   const void* Wp; int ldw;   // packed weights (atomnas_pack_weights) and their row pitch

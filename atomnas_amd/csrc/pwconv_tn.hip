@@ -1,8 +1,10 @@
 // Weight-gradient GEMMs of the pointwise (1x1) convolutions on gfx950 (split out of pwconv.hip in round 6):
 //   gemm_tn  : Out[i,j] += sum_m pro(U)[m,i] * pro(V)[m,j]            (reduction over M = batch x pixels)
 // behind atomnas_pw_gemm_tn: dW of ConvBNReLU(inp, hid, 1) (models/mobilenet_base.py:316-320), of the linear projection (:338), of the
-// last 1x1 conv (models/mobilenet_supernet.py:148-153) and of the classifier (:160-163).  k_gemm_tn: any storage type (the fp32 parity
-// mode); k_gemm_tn2: bf16, 128-row slabs with transposing LDS reads; k_gemm_tn3: bf16, single-stream late-stage shapes on an LDS-DMA ring.
+// last 1x1 conv (models/mobilenet_supernet.py:148-153) and of the classifier (:160-163).  Three kernel families, compiled for exactly
+// the instances the host side (end of the file) can reach: k_gemm_tn3 ("dma": bf16, single-stream late-stage shapes on an LDS-DMA
+// ring), k_gemm_tn2 ("slab": bf16, 64 / 128-row slabs staged through registers, transposing LDS reads) and k_gemm_tn ("generic": the
+// fp32 parity mode).
 #include "pwconv.h"
 
 namespace atomnas {
@@ -102,52 +104,24 @@ __global__ __launch_bounds__(256) void k_gemm_tn(Operand U, int NU, Operand V, i
 }
 
 
-// ------------------------------------------------------------------------------------------------ gemm_tn, bf16, transposed LDS
-// Same contract as k_gemm_tn, restructured for bandwidth: 128-row slabs (4x more bytes in flight per barrier), and the
-// operands are written to LDS TRANSPOSED ([column][row], two rows packed per 32-bit store, conflict-free) so that every MFMA
-// fragment -- 8 consecutive rows of one column -- is a single ds_read_b128 instead of eight 16-bit reads.
-#ifndef TN2_COALESCED
-#define TN2_COALESCED 0   // staging loads: 0 = lanes along rows (16 bytes of 64 different lines per instruction, revisited from L1
-                          // by the next channel groups), 1 = lanes along channels (whole 128-byte segments).  Measured in situ
-                          // (bs 256 step): 11.8 ms vs 13.0 ms per step for all weight-gradient GEMMs -- rows win.
-#endif
-#ifndef TN2_KS_UNROLL
-#define TN2_KS_UNROLL 2
-#endif
-#ifndef TN_TIMING
-#define TN_TIMING 0   // s_memtime phase accounting of k_gemm_tn2 (tools/tnbench2.py, experiment builds only)
-#endif
-#if TN_TIMING
-__device__ unsigned long long g_tn_timing[8];
-#define TN_MARK(i)                                                     \
-  {                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                 \
-    const unsigned long long tn_ = __builtin_readcyclecounter();       \
-    tacc[i] += tn_ - tlast;                                            \
-    tlast = tn_;                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                 \
-  }
-#else
-#define TN_MARK(i)
-#endif
-
-
-// TR (round 4): the operands stay row-major in LDS -- [32-row chunk][16-column tile][32][16] subtiles, filled with ONE 16-byte store per
-// (row, 8 channels) piece -- and the k-major MFMA fragments are read with ds_read_b64_tr_b16, gfx950's transposing LDS read (two per
-// fragment; semantics checked with tools/probe/trread.hip: lane (c, g) element e <- the 8-byte segment the group's sub-lane 4 e + c / 4
-// points at, its element c % 4).  Without it every (row pair, 8 channels) unit is transposed by hand: eight packs and eight 4-byte LDS
-// stores, which -- with the loads -- was where the kernel's wave cycles went (profiles/r03_tn_phase_timing.txt).
-template <int UMODE, int VMODE, int UTT, int VTT, int ROWS, bool TR>
+// ------------------------------------------------------------------------------------------------ gemm_tn, bf16, slabs staged through registers
+// Same contract as k_gemm_tn, restructured for bandwidth: 64 / 128-row slabs (more bytes in flight per barrier).  The operands stay
+// row-major in LDS -- [32-row chunk][16-column tile][32][16] subtiles, filled with ONE 16-byte store per (row, 8 channels) piece -- and
+// the k-major MFMA fragments are read with ds_read_b64_tr_b16, gfx950's transposing LDS read (two per fragment; semantics checked with
+// tools/probe/trread.hip: lane (c, g) element e <- the 8-byte segment the group's sub-lane 4 e + c / 4 points at, its element c % 4).
+// (Until round 4 every (row pair, 8 channels) unit was transposed by hand, eight packs and eight 4-byte LDS stores, which -- with the
+// loads -- was where the kernel's wave cycles went: profiles/r03_tn_phase_timing.txt.)
+template <int UMODE, int VMODE, int UTT, int VTT, int ROWS>
 __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, int NV, float* __restrict__ out, long si, long sj, long M,
                                                   long rows_per_block, int nchunks, int vt, int uz, int xcd_aware, float* __restrict__ ws) {
   using T = bf16_t;
   using MM = Mma<T>;
   constexpr int VW = 64 * VTT;      // V columns per workgroup: each wave owns VTT tiles of 16 (the U tile is re-read per V tile:
                                     // wider V tiles halve that traffic where U is not narrow)
-  constexpr int RP = ROWS + 8;      // transposed row pitch (elements): 16 consecutive columns land on 16 distinct 16-byte slots
+  constexpr int RP = ROWS + 8;      // elements per column of the two LDS regions (the pitch of the hand-transposed layout they were sized for)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* s_v = reinterpret_cast<T*>(smem_raw);          // [VW][RP]   (TR: [ROWS / 32][VW / 16][32][16])
-  T* s_u = s_v + VW * RP;                           // [16*UTT][RP]   (TR: [ROWS / 32][UTT][32][16]; the region is the same size or smaller)
+  T* s_v = reinterpret_cast<T*>(smem_raw);          // [ROWS / 32][VW / 16][32][16] inside a region of VW * RP elements
+  T* s_u = s_v + VW * RP;                           // [ROWS / 32][UTT][32][16] inside 16 * UTT * RP
   float* s_cv = reinterpret_cast<float*>(s_u + 16 * UTT * RP);       // [3][VW]      prologue coefficients of the V tile
   float* s_cu = s_cv + 3 * VW;                                       // [3][16*UTT]  ... of the U tile
 
@@ -187,10 +161,6 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
   __syncthreads();
 
   const int ugroups = ut * 2;   // 8-channel groups per row
-#if TN_TIMING
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tlast = __builtin_readcyclecounter();
-#endif
   // Round 3: the staging loads of a slab are issued TOGETHER, one slab ahead, and only then transformed and stored transposed.
   // Before, every staging iteration (two rows x 8 channels per thread) loaded and immediately consumed its own data: 10 memory
   // round trips per 128-row slab (139 us for the 7x7 projection weight gradient, 87 MB of operands).  All loads are unconditional
@@ -203,18 +173,16 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
   // work unit (row pair rp, 8-channel group cg) of a thread.  Slab-major operands: consecutive lanes take the two halves of a slab
   // row and then the next row pair, so that a wave's two loads of a unit cover 2 KB of ONE slab contiguously (16 lines of 128 bytes)
   // -- with the lanes along the rows of one channel group, every load instruction touched 32 lines for 1 KB of payload and the issue of
-  // a slab's loads was 42-51 % of the kernel's wave cycles (tools/tntiming.py, r03).  Plain operands: lanes along the rows.
-  auto unit = [&](int idx, int groups, bool slab, int& cg, int& rp) {
+  // a slab's loads was 42-51 % of the kernel's wave cycles (profiles/r03_tn_phase_timing.txt).  Plain operands: lanes along the rows
+  // (16 bytes of 64 different lines per instruction, revisited from L1 by the next channel groups) -- against lanes along the channels
+  // (whole 128-byte segments) 11.8 vs 13.0 ms per bs-256 step for all weight-gradient GEMMs: rows win.
+  auto unit = [&](int idx, bool slab, int& cg, int& rp) {
     if (slab) {
       const int u = idx >> 1;
       rp = u % (ROWS / 2);
       cg = (u / (ROWS / 2)) * 2 + (idx & 1);
     } else {
-#if TN2_COALESCED
-      cg = idx % groups; rp = idx / groups;
-#else
       rp = idx % (ROWS / 2); cg = idx / (ROWS / 2);
-#endif
     }
   };
   const bool vslab = V.ss1 != 0, uslab = U.ss1 != 0;
@@ -227,7 +195,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
   auto v_unit = [&](int i, int& rp, long& c1, long& c2) {
     int cg;
     const int idx = tid + 256 * i;
-    unit(idx < (ROWS / 2) * (VW / 8) ? idx : 0, VW / 8, vslab, cg, rp);
+    unit(idx < (ROWS / 2) * (VW / 8) ? idx : 0, vslab, cg, rp);
     int k = v0 + cg * 8;
     k = k < NV ? k : K8V - 8;
     c1 = lay_off(0, k, V.ld1, V.ss1);
@@ -236,7 +204,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
   auto u_unit = [&](int i, int& rp, long& c1, long& c2) {
     int cg;
     const int idx = tid + 256 * i;
-    unit(idx < (ROWS / 2) * ugroups ? idx : 0, ugroups, uslab, cg, rp);
+    unit(idx < (ROWS / 2) * ugroups ? idx : 0, uslab, cg, rp);
     int k = u0 + cg * 8;
     k = k < NU ? k : K8U - 8;
     c1 = lay_off(0, k, U.ld1, U.ss1);
@@ -351,28 +319,17 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
       int cg, rp;
       const int idx = tid + 256 * i;
       const bool active = idx < (ROWS / 2) * (VW / 8);
-      unit(active ? idx : 0, VW / 8, vslab, cg, rp);
+      unit(active ? idx : 0, vslab, cg, rp);
       float a[8], bb[8];
       const float* lc = s_cv + cg * 8;
       const bool kv = v0 + cg * 8 < NV;
       xform(std::integral_constant<int, VMODE>{}, V, rva[i][0], rvx[V2 ? i : 0][0], row_guard || v_tail, kv && (r0 + 2 * rp) < r_end, lc, lc + VW, lc + 2 * VW, a);
       xform(std::integral_constant<int, VMODE>{}, V, rva[i][1], rvx[V2 ? i : 0][1], row_guard || v_tail, kv && (r0 + 2 * rp + 1) < r_end, lc, lc + VW, lc + 2 * VW, bb);
-      const int rot = TN2_COALESCED ? 2 * (cg >> 1) : 0;
       if (active) {
-        if constexpr (TR) {
-          // row-major subtiles [2 rp / 32][cg / 2][32][16]: one 16-byte store per row
-          T* d = s_v + (((2 * rp) >> 5) * (VW / 16) + (cg >> 1)) * 512 + ((2 * rp) & 31) * 16 + (cg & 1) * 8;
-          *reinterpret_cast<bf16x8*>(d) = MM::pack(a);
-          *reinterpret_cast<bf16x8*>(d + 16) = MM::pack(bb);
-        } else {
-#pragma unroll
-          for (int ii = 0; ii < 8; ++ii) {
-            const int e = (ii + rot) & 7;
-            bf16x2 pk;
-            pk[0] = (bf16_t)a[e]; pk[1] = (bf16_t)bb[e];
-            *reinterpret_cast<bf16x2*>(&s_v[(cg * 8 + e) * RP + 2 * rp]) = pk;
-          }
-        }
+        // row-major subtiles [2 rp / 32][cg / 2][32][16]: one 16-byte store per row
+        T* d = s_v + (((2 * rp) >> 5) * (VW / 16) + (cg >> 1)) * 512 + ((2 * rp) & 31) * 16 + (cg & 1) * 8;
+        *reinterpret_cast<bf16x8*>(d) = MM::pack(a);
+        *reinterpret_cast<bf16x8*>(d + 16) = MM::pack(bb);
       }
     }
 #pragma unroll
@@ -380,31 +337,20 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
       int cg, rp;
       const int idx = tid + 256 * i;
       const bool active = idx < (ROWS / 2) * ugroups;
-      unit(active ? idx : 0, ugroups, uslab, cg, rp);
+      unit(active ? idx : 0, uslab, cg, rp);
       float a[8], bb[8];
       const float* lc = s_cu + cg * 8;
       const bool kv = u0 + cg * 8 < NU;
       xform(std::integral_constant<int, UMODE>{}, U, rua[i][0], rux[U2 ? i : 0][0], row_guard || u_tail, kv && (r0 + 2 * rp) < r_end, lc, lc + 16 * UTT, lc + 32 * UTT, a);
       xform(std::integral_constant<int, UMODE>{}, U, rua[i][1], rux[U2 ? i : 0][1], row_guard || u_tail, kv && (r0 + 2 * rp + 1) < r_end, lc, lc + 16 * UTT, lc + 32 * UTT, bb);
-      const int rot = TN2_COALESCED ? 2 * (cg >> 1) : 0;
       if (active) {
-        if constexpr (TR) {
-          T* d = s_u + (((2 * rp) >> 5) * UTT + (cg >> 1)) * 512 + ((2 * rp) & 31) * 16 + (cg & 1) * 8;
-          *reinterpret_cast<bf16x8*>(d) = MM::pack(a);
-          *reinterpret_cast<bf16x8*>(d + 16) = MM::pack(bb);
-        } else {
-#pragma unroll
-          for (int ii = 0; ii < 8; ++ii) {
-            const int e = (ii + rot) & 7;
-            bf16x2 pk;
-            pk[0] = (bf16_t)a[e]; pk[1] = (bf16_t)bb[e];
-            *reinterpret_cast<bf16x2*>(&s_u[(cg * 8 + e) * RP + 2 * rp]) = pk;
-          }
-        }
+        T* d = s_u + (((2 * rp) >> 5) * UTT + (cg >> 1)) * 512 + ((2 * rp) & 31) * 16 + (cg & 1) * 8;
+        *reinterpret_cast<bf16x8*>(d) = MM::pack(a);
+        *reinterpret_cast<bf16x8*>(d + 16) = MM::pack(bb);
       }
     }
   };
-  // TR: fragment of subtile `st` (a [32][16] row-major block, 1 KB) -- k = 8 q + e along the rows, column j: two transposing reads
+  // fragment of subtile `sub` (a [32][16] row-major block, 1 KB) -- k = 8 q + e along the rows, column j: two transposing reads
   // (rows 8 q .. 8 q + 3 and 8 q + 4 .. 8 q + 7); every lane passes the address of its 8-byte segment: row 8 q + j / 4, columns 4 (j % 4) ..
   const unsigned tr_lane = (unsigned)(((8 * q + (j >> 2)) * 16 + 4 * (j & 3)) * 2);
   auto tr_frag = [&](const T* sub) {
@@ -416,61 +362,34 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
   };
   issue(r_beg);
   for (long r0 = r_beg; r0 < r_end; r0 += ROWS) {
-    TN_MARK(5)
     stage(r0);
-    TN_MARK(0)
     issue(r0 + ROWS);   // the next slab flies during the MFMA phase (past the chunk: clamped rows, values never used)
-    TN_MARK(1)
     __syncthreads();
-    TN_MARK(2)
-#pragma unroll TN2_KS_UNROLL   // full unrolling hoists all fragment reads: 162 VGPRs for 6 accumulator tiles, 2 waves per SIMD
+#pragma unroll 2   // full unrolling hoists all fragment reads: 162 VGPRs for 6 accumulator tiles, 2 waves per SIMD
     for (int ks = 0; ks < ROWS / 32; ++ks) {
-      if constexpr (TR) {
-        // all fragment reads of the k-step are issued, ONE wait (the asm reads are invisible to the compiler's counters), then the MFMAs
-        TrFrag bfp[VTT], afp[UTT];
+      // all fragment reads of the k-step are issued, ONE wait (the asm reads are invisible to the compiler's counters), then the MFMAs
+      TrFrag bfp[VTT], afp[UTT];
 #pragma unroll
-        for (int v = 0; v < VTT; ++v) bfp[v] = tr_frag(s_v + (ks * (VW / 16) + 4 * v + wave) * 512);
+      for (int v = 0; v < VTT; ++v) bfp[v] = tr_frag(s_v + (ks * (VW / 16) + 4 * v + wave) * 512);
 #pragma unroll
-        for (int t = 0; t < UTT; ++t)
-          if (t < ut) afp[t] = tr_frag(s_u + (ks * UTT + t) * 512);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        bf16x8 bf[VTT];
+      for (int t = 0; t < UTT; ++t)
+        if (t < ut) afp[t] = tr_frag(s_u + (ks * UTT + t) * 512);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      bf16x8 bf[VTT];
 #pragma unroll
-        for (int v = 0; v < VTT; ++v) bf[v] = __builtin_shufflevector(bfp[v].lo, bfp[v].hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      for (int v = 0; v < VTT; ++v) bf[v] = __builtin_shufflevector(bfp[v].lo, bfp[v].hi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
-        for (int t = 0; t < UTT; ++t) {
-          if (t < ut) {
-            const bf16x8 af = __builtin_shufflevector(afp[t].lo, afp[t].hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      for (int t = 0; t < UTT; ++t) {
+        if (t < ut) {
+          const bf16x8 af = __builtin_shufflevector(afp[t].lo, afp[t].hi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
-            for (int v = 0; v < VTT; ++v) acc[v][t] = MM::mma(af, bf[v], acc[v][t]);
-          }
-        }
-      } else {
-        bf16x8 bf[VTT];
-#pragma unroll
-        for (int v = 0; v < VTT; ++v) bf[v] = *reinterpret_cast<const bf16x8*>(&s_v[(64 * v + 16 * wave + j) * RP + 32 * ks + 8 * q]);
-#pragma unroll
-        for (int t = 0; t < UTT; ++t) {
-          if (t < ut) {
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(&s_u[(16 * t + j) * RP + 32 * ks + 8 * q]);
-#pragma unroll
-            for (int v = 0; v < VTT; ++v) acc[v][t] = MM::mma(af, bf[v], acc[v][t]);
-          }
+          for (int v = 0; v < VTT; ++v) acc[v][t] = MM::mma(af, bf[v], acc[v][t]);
         }
       }
     }
-    TN_MARK(3)
     __syncthreads();
-    TN_MARK(4)
   }
-#if TN_TIMING
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) atomicAdd(&g_tn_timing[i], tacc[i]);
-    atomicAdd(&g_tn_timing[7], (unsigned long long)((r_end - r_beg + ROWS - 1) / ROWS));
-  }
-#endif
 
 #pragma unroll
   for (int v = 0; v < VTT; ++v) {
@@ -491,66 +410,6 @@ __global__ __launch_bounds__(256) void k_gemm_tn2(Operand U, int NU, Operand V, 
       }
     }
   }
-}
-
-template <int UTT, int VTT, int ROWS>
-static int launch_tn2_cfg(int umode, const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M,
-                          float* ws, long ws_floats, hipStream_t st) {
-  const int vt = (NV + 64 * VTT - 1) / (64 * VTT), uz = (NU + 16 * UTT - 1) / (16 * UTT);
-  const size_t lds = (size_t)(64 * VTT + 16 * UTT) * (ROWS + 8) * sizeof(bf16_t) + (size_t)3 * (64 * VTT + 16 * UTT) * sizeof(float);
-  // row chunks so that the grid is one round of resident workgroups (at least two slabs per workgroup)
-  constexpr int xcd_env = 1;
-  constexpr int tr_on = 1;   // experiment switch: transposing LDS reads (round 4)
-#define TN2_CASE(UM, VM)                                                                                                      \
-  {                                                                                                                           \
-    auto kern = tr_on ? k_gemm_tn2<UM, VM, UTT, VTT, ROWS, true> : k_gemm_tn2<UM, VM, UTT, VTT, ROWS, false>;                 \
-    const long resident = (long)num_cus() * resident_per_cu(kern, 256, lds);                                                  \
-    long chunks = resident / ((long)vt * uz);                                                                                 \
-    if (chunks > M / (2 * ROWS)) chunks = M / (2 * ROWS);                                                                     \
-    if (chunks > max_chunks) chunks = max_chunks;   /* every row chunk owns one partial output in the workspace */           \
-    int xcd = xcd_env;                                                                                                        \
-    if (chunks < 8) xcd = 0; /* fewer chunks than XCDs: plain order */                                                        \
-    if (xcd) chunks = chunks / 8 * 8; /* equal work per XCD */                                                                \
-    if (chunks < 1) chunks = 1;                                                                                               \
-    const long rows = (M + chunks - 1) / chunks;                                                                              \
-    chunks = (M + rows - 1) / rows;                                                                                           \
-    nparts = chunks;                                                                                                          \
-    dim3 grid((unsigned)((xcd ? (chunks + 7) / 8 * 8 : chunks) * vt * uz)), block(256);                                       \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, U, NU, V, NV, out, si, sj, M, rows, (int)chunks, vt, uz, xcd,             \
-                       chunks > 1 ? ws : nullptr);                                                                            \
-  }
-  const long max_chunks = (ws && (long)NU * NV > 0) ? ws_floats / ((long)NU * NV) : 1;   // < 2: single chunk, direct accumulation
-  long nparts = 1;
-  if (umode == PRO_NONE && vmode == PRO_NONE) TN2_CASE(PRO_NONE, PRO_NONE)
-  else if (umode == PRO_NONE && vmode == PRO_BNBWD) TN2_CASE(PRO_NONE, PRO_BNBWD)
-  else if (umode == PRO_BNBWD && vmode == PRO_BNRELU) TN2_CASE(PRO_BNBWD, PRO_BNRELU)
-  else if (umode == PRO_BNRELU && vmode == PRO_BNBWD) TN2_CASE(PRO_BNRELU, PRO_BNBWD)
-  else if (umode == PRO_BNBWD && vmode == PRO_NONE) TN2_CASE(PRO_BNBWD, PRO_NONE)
-  else if (umode == PRO_NONE && vmode == PRO_BNRELU) TN2_CASE(PRO_NONE, PRO_BNRELU)   /* U = atomnas_bnbwd_apply's output */
-  else { set_error("gemm_tn: unsupported prologue pair (%d,%d)", umode, vmode); return 1; }
-#undef TN2_CASE
-  if (int rc = check_launch("gemm_tn2")) return rc;
-  if (nparts > 1) return reduce_parts(ws, (long)NU * NV, (int)nparts, (long)NU * NV, out, NV, si, sj, st);
-  return 0;
-}
-
-// V tile width.  The U slab is re-staged (transposed) for every V tile, so with a wide U (many accumulator tiles) a 128-column V tile
-// halves that work at the price of LDS / registers.  Measured in situ per shape (bs 256 step, after the early-stage weight gradients
-// moved into the fused backward kernels; profiles/r02_bs256_per_shape_timing.txt): NU 40..96 (4 / 6 accumulator tiles): 128 columns
-// on 64-row slabs -15..-30 %; NU 320 (two U tiles of 160): 128 columns on 128-row slabs -20 %; NU 192 (12 tiles): 64 columns stay
-// best (+20..35 % otherwise).  ATOMNAS_TN_WIDE = 0 / 1 / 2 forces one form (A/B).
-template <int UTT>
-static int launch_tn2_ut(int umode, const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M,
-                         float* ws, long ws_floats, hipStream_t st) {
-  constexpr int wide_env = -1;
-  if constexpr (UTT >= 4 && UTT <= 12) {
-    // r03, after the staging rewrite (same-call A/B over the step's shapes, ATOMNAS_TN_WIDE=0/1/2: 4.36 / 3.46 / 3.88 ms): 128-column V
-    // tiles on 64-row slabs win for every U width (r02 had 64-column tiles for 12 U tiles and 128-row slabs for 10)
-    const int wide = wide_env >= 0 ? wide_env : 1;
-    if (wide == 1 && NV >= 256) return launch_tn2_cfg<UTT, 2, 64>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-    if (wide == 2 && NV >= 256) return launch_tn2_cfg<UTT, 2, 128>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  }
-  return launch_tn2_cfg<UTT, 1, 128>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
 }
 
 // ------------------------------------------------------------------------------------------------ gemm_tn, LDS-DMA form (round 4)
@@ -731,113 +590,167 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn3(Operand U, int NU, Operand 
   }
 }
 
-// -1: not one of this kernel's cases
-template <int UTT>
-static int launch_tn3_cfg(const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M, float* ws,
-                          long ws_floats, hipStream_t st) {
-  const int vt = (NV + 127) / 128, uz = (NU + 16 * UTT - 1) / (16 * UTT);
-  // ring depth: as many stages in flight as leave room for two workgroups per CU (ATOMNAS_TN3_DEPTH: experiment switch)
-  constexpr int depth_env = 0;
-  const int depth = depth_env ? depth_env : ((size_t)4 * (8 + UTT) * 1024 * 2 + 4096 <= max_lds_bytes() ? 4 : 3);
-  const size_t lds = (size_t)depth * (8 + UTT) * 1024;
-  if (lds > max_lds_bytes()) return -1;
-  constexpr bool dbg = false;
-  const long max_chunks = (ws && (long)NU * NV > 0) ? ws_floats / ((long)NU * NV) : 1;
-  long nparts = 1;
-#define TN3_CASE(VP)                                                                                                          \
-  {                                                                                                                           \
-    auto kern = depth == 4 ? k_gemm_tn3<UTT, VP, 4> : (depth == 3 ? k_gemm_tn3<UTT, VP, 3> : k_gemm_tn3<UTT, VP, 2>);          \
-    const long resident = (long)num_cus() * resident_per_cu(kern, 256, lds);                                                  \
-    if (dbg) fprintf(stderr, "tn3: M %ld NU %d NV %d UTT %d depth %d lds %zu per_cu %ld\n", M, NU, NV, UTT, depth, lds, resident / num_cus()); \
-    long chunks = resident / ((long)vt * uz);                                                                                 \
-    if (chunks > M / 128) chunks = M / 128;   /* at least four stages per workgroup */                                        \
-    if (chunks > max_chunks) chunks = max_chunks;                                                                             \
-    chunks = chunks / 8 * 8;   /* equal work per XCD */                                                                       \
-    if (chunks < 8) return -1;                                                                                                \
-    long rows = (M + chunks - 1) / chunks;                                                                                    \
-    rows = (rows + 31) / 32 * 32;   /* whole stages: only the tensor's last chunk has a ragged one */                         \
-    chunks = (M + rows - 1) / rows;                                                                                           \
-    nparts = chunks;                                                                                                          \
-    dim3 grid((unsigned)((chunks + 7) / 8 * 8 * vt * uz)), block(256);                                                        \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, U, NU, V, NV, out, si, sj, M, rows, (int)chunks, vt, uz, ws);              \
-  }
-  if (vmode == PRO_BNRELU) TN3_CASE(true) else TN3_CASE(false)
-#undef TN3_CASE
-  if (int rc = check_launch("gemm_tn3")) return rc;
-  return reduce_parts(ws, (long)NU * NV, (int)nparts, (long)NU * NV, out, NV, si, sj, st);
+// ------------------------------------------------------------------------------------------------ host side
+// atomnas_pw_gemm_tn validates its arguments into ONE TnArgs block; launch_tn is the ordered list of kernel families (bf16: dma,
+// slab; fp32: generic).  A family is a pair: tn_<family>_plan is the COMPLETE accept / reject decision, a pure function of TnArgs
+// (the switch, the thresholds, the instance, LDS bytes, row chunks, grid), and leaves all of it in the family's plan struct;
+// tn_<family>_launch runs an accepted plan and cannot decline.  Every k_gemm_tn* instance the file compiles is one a plan can pick.
+struct TnArgs {
+  int umode; Operand U; int NU;   // prologue (PRO_*), operand and columns of the two sides
+  int vmode; Operand V; int NV;
+  float* out; long si, sj, M;     // out[i * si + j * sj] += sum over M rows
+  float* ws; long ws_floats;      // caller's scratch for the per-row-chunk partial outputs (may be null)
+  hipStream_t st;
+};
+
+// f receives the one of Vs... that equals v as a compile-time constant (the plans leave v in the list)
+template <int... Vs, typename F> static int for_value(int v, F&& f) {
+  int rc = 1;
+  (void)((v == Vs ? (rc = f(IC<Vs>{}), true) : false) || ...);
+  return rc;
+}
+// f receives the prologue pair (u_mode, v_mode) as compile-time constants: the six pairs the training step uses; any other is an error
+template <typename F> static int for_pair(int umode, int vmode, F&& f) {
+#define X(UM, VM) if (umode == UM && vmode == VM) return f(IC<UM>{}, IC<VM>{});
+  X(PRO_NONE, PRO_NONE) X(PRO_NONE, PRO_BNBWD) X(PRO_BNBWD, PRO_BNRELU) X(PRO_BNRELU, PRO_BNBWD) X(PRO_BNBWD, PRO_NONE)
+  X(PRO_NONE, PRO_BNRELU)   // U = atomnas_bnbwd_apply's output
+#undef X
+  set_error("gemm_tn: unsupported prologue pair (%d,%d)", umode, vmode);
+  return 1;
 }
 
-static int launch_tn3(int umode, const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M,
-                      float* ws, long ws_floats, hipStream_t st) {
-  static const int on = getenv("ATOMNAS_TN_DMA") ? atoi(getenv("ATOMNAS_TN_DMA")) : 1;   // experiment switch
-  // single-stream weight gradients of wide hidden tensors: U without prologue, V none / BNRELU, a workspace for >= 8 row chunks
-  if (!on || umode != PRO_NONE || (vmode != PRO_NONE && vmode != PRO_BNRELU) || !ws || NV < 256 || NU < 32 || M < 1024) return -1;
-  if (vmode == PRO_BNRELU && !(V.c1 && V.c2)) return -1;
+// Accumulator tiles per wave (= U tiles of 16 columns) of the bf16 instances: fewer tiles -> fewer AGPRs -> more waves per SIMD.
+// 10: two U tiles of <= 160 columns; 20: wider than 320 (k_gemm_tn2 only); k_gemm_tn3 has no 2-tile instance and takes 4.
+static int tn_utt(int NU, bool dma) {
   const int ut = (NU + 15) / 16;
-  if (ut <= 4) return launch_tn3_cfg<4>(U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 6) return launch_tn3_cfg<6>(U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 12) return launch_tn3_cfg<12>(U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 20) return launch_tn3_cfg<10>(U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);   // two U tiles of <= 160 columns
-  return -1;
+  return ut <= 2 ? (dma ? 4 : 2) : ut <= 4 ? 4 : ut <= 6 ? 6 : ut <= 12 ? 12 : ut <= 20 ? 10 : 20;
 }
 
-static int launch_tn2(int umode, const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M,
-                      float* ws, long ws_floats, hipStream_t st) {
-  {
-    const int rc = launch_tn3(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-    if (rc >= 0) return rc;
-  }
-  // accumulator tiles per wave (= U tiles of 16 columns): fewer tiles -> fewer AGPRs -> more waves per SIMD
-  const int ut = (NU + 15) / 16;
-  if (ut <= 2) return launch_tn2_ut<2>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 4) return launch_tn2_ut<4>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 6) return launch_tn2_ut<6>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 12) return launch_tn2_ut<12>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  if (ut <= 20) return launch_tn2_ut<10>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);   // two U tiles of <= 160 columns
-  return launch_tn2_ut<20>(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-}
-
-template <typename T>
-static int launch_tn(int umode, const Operand& U, int NU, int vmode, const Operand& V, int NV, float* out, long si, long sj, long M,
-                     float* ws, long ws_floats, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) return launch_tn2(umode, U, NU, vmode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  const int vt = (NV + 63) / 64, uz = (NU + 16 * UT_MAX - 1) / (16 * UT_MAX);
-  // enough row chunks to fill the chip, but at least 8 slabs of 32 rows per block
-  long chunks = (1024 + (long)vt * uz - 1) / ((long)vt * uz);
-  const long max_chunks = ws ? ws_floats / ((long)NU * NV) : 1;   // every row chunk owns one partial output in the workspace
-  if (chunks > max_chunks) chunks = max_chunks;
-  if (chunks < 1) chunks = 1;
-  long rows = (M + chunks - 1) / chunks;
-  if (rows < 8 * TN_ROWS) rows = 8 * TN_ROWS;
-  rows = (rows + TN_ROWS - 1) / TN_ROWS * TN_ROWS;
+// Row chunks.  Every chunk owns one partial output in the workspace (tn_ws_cap; < 2: one chunk, accumulated directly into out) and
+// one workgroup per output tile.  Each plan caps the chunks it `want`s in its own way; tn_split turns them into rows per chunk (at
+// least min_rows, a multiple of quantum) and the chunks that many rows make.
+static long tn_ws_cap(const TnArgs& a) { return a.ws ? a.ws_floats / ((long)a.NU * a.NV) : 1; }
+static void tn_split(long M, long want, long min_rows, long quantum, long& chunks, long& rows) {
+  if (want < 1) want = 1;
+  rows = (M + want - 1) / want;
+  if (rows < min_rows) rows = min_rows;
+  rows = (rows + quantum - 1) / quantum * quantum;
   chunks = (M + rows - 1) / rows;
-  dim3 grid((unsigned)chunks, vt, uz), block(256);
-#define TN_CASE(UM, VM) \
-  hipLaunchKernelGGL((k_gemm_tn<T, UM, VM>), grid, block, 0, st, U, NU, V, NV, out, si, sj, M, rows, chunks > 1 ? ws : nullptr)
-  if (umode == PRO_NONE && vmode == PRO_NONE) TN_CASE(PRO_NONE, PRO_NONE);
-  else if (umode == PRO_NONE && vmode == PRO_BNBWD) TN_CASE(PRO_NONE, PRO_BNBWD);
-  else if (umode == PRO_BNBWD && vmode == PRO_BNRELU) TN_CASE(PRO_BNBWD, PRO_BNRELU);
-  else if (umode == PRO_BNRELU && vmode == PRO_BNBWD) TN_CASE(PRO_BNRELU, PRO_BNBWD);
-  else if (umode == PRO_BNBWD && vmode == PRO_NONE) TN_CASE(PRO_BNBWD, PRO_NONE);
-  else if (umode == PRO_NONE && vmode == PRO_BNRELU) TN_CASE(PRO_NONE, PRO_BNRELU);
-  else { set_error("gemm_tn: unsupported prologue pair (%d,%d)", umode, vmode); return 1; }
-#undef TN_CASE
-  if (int rc = check_launch("gemm_tn")) return rc;
-  if (chunks > 1) return reduce_parts(ws, (long)NU * NV, (int)chunks, (long)NU * NV, out, NV, si, sj, st);
+}
+// after the family's launch: the partials are summed in chunk order
+static int tn_finish(const char* what, const TnArgs& a, long chunks) {
+  if (int rc = check_launch(what)) return rc;
+  if (chunks > 1) return reduce_parts(a.ws, (long)a.NU * a.NV, (int)chunks, (long)a.NU * a.NV, a.out, a.NV, a.si, a.sj, a.st);
   return 0;
+}
+
+// ---- dma: single-stream weight gradients of wide hidden tensors on the LDS-DMA ring (k_gemm_tn3): U without prologue, V none /
+// BNRELU, a workspace for >= 8 row chunks (one per XCD)
+using TnDmaKernel = decltype(&k_gemm_tn3<4, false, 4>);
+struct TnDmaPlan { TnDmaKernel kern; int utt, vt, uz; size_t lds; long chunks, rows; unsigned grid; };
+constexpr int DMA_MINNU = 32, DMA_MINNV = 256;
+constexpr long DMA_MINM = 1024, DMA_MINROWS = 128;   // at least four 32-row stages per workgroup
+// ring depth: as many stages in flight as leave room for two workgroups in the CU's 160 KiB (4; 3 for twelve U tiles).  Measured:
+// depth 2 / 3 / 4 makes no difference (the partial-output traffic, chunks x |out|, is what is left at 7 x 7).
+constexpr int tn3_depth(int utt) { return 2 * (4 * (8 + utt) * 1024) + 4096 <= 160 * 1024 ? 4 : 3; }
+static bool tn_dma_plan(const TnArgs& a, TnDmaPlan& p) {
+  static const int on = getenv("ATOMNAS_TN_DMA") ? atoi(getenv("ATOMNAS_TN_DMA")) : 1;   // experiment switch, the only one of this file
+  if (!on || a.umode != PRO_NONE || (a.vmode != PRO_NONE && a.vmode != PRO_BNRELU) || !a.ws) return false;
+  if (a.NV < DMA_MINNV || a.NU < DMA_MINNU || a.M < DMA_MINM) return false;
+  p.utt = tn_utt(a.NU, true);
+  if (for_value<4, 6, 12, 10>(p.utt, [&](auto utt) {
+        constexpr int UTT = decltype(utt)::value, DEPTH = tn3_depth(UTT);
+        p.kern = a.vmode == PRO_BNRELU ? k_gemm_tn3<UTT, true, DEPTH> : k_gemm_tn3<UTT, false, DEPTH>;
+        p.lds = (size_t)DEPTH * (8 + UTT) * 1024;
+        return 0;
+      }))
+    return false;   // NU > 320
+  if (p.lds > max_lds_bytes()) return false;
+  p.vt = (a.NV + 127) / 128, p.uz = (a.NU + 16 * p.utt - 1) / (16 * p.utt);
+  const long tiles = (long)p.vt * p.uz;
+  long want = (long)num_cus() * resident_per_cu(p.kern, 256, p.lds) / tiles;   // one round of resident workgroups
+  if (want > a.M / DMA_MINROWS) want = a.M / DMA_MINROWS;
+  if (want > tn_ws_cap(a)) want = tn_ws_cap(a);
+  want = want / 8 * 8;   // equal work per XCD
+  if (want < 8) return false;
+  tn_split(a.M, want, 0, 32, p.chunks, p.rows);   // whole stages: only the tensor's last chunk has a ragged one
+  p.grid = (unsigned)((p.chunks + 7) / 8 * 8 * tiles);
+  return true;
+}
+static int tn_dma_launch(const TnDmaPlan& p, const TnArgs& a) {
+  hipLaunchKernelGGL(p.kern, dim3(p.grid), dim3(256), p.lds, a.st, a.U, a.NU, a.V, a.NV, a.out, a.si, a.sj, a.M, p.rows, (int)p.chunks, p.vt,
+                     p.uz, a.ws);
+  return tn_finish("gemm_tn3", a, p.chunks);
+}
+
+// ---- slab: every bf16 shape and supported prologue pair (k_gemm_tn2); false: the pair is unsupported, for_pair has set the error
+// V tile width.  The U slab is re-staged for every V tile, so a 128-column V tile halves that work at the price of LDS / registers.
+// Measured (r03, same-call A/B over the step's shapes: 64 columns x 128 rows 4.36 ms, 128 x 64 3.46 ms, 128 x 128 3.88 ms): 128-column
+// V tiles on 64-row slabs win for every U width of 4 .. 12 tiles where V has them (profiles/r03_switch_sweeps.txt).
+using TnSlabKernel = decltype(&k_gemm_tn2<PRO_NONE, PRO_NONE, 2, 1, 128>);
+struct TnSlabPlan { TnSlabKernel kern; int utt, vtt, slab_rows, vt, uz; size_t lds; long chunks, rows; int xcd; unsigned grid; };
+constexpr int SLAB_WIDE_MINNV = 256;
+static bool tn_slab_plan(const TnArgs& a, TnSlabPlan& p) {
+  p.utt = tn_utt(a.NU, false);
+  const bool wide = p.utt >= 4 && p.utt <= 12 && a.NV >= SLAB_WIDE_MINNV;
+  p.vtt = wide ? 2 : 1, p.slab_rows = wide ? 64 : 128;
+  if (for_pair(a.umode, a.vmode, [&](auto um, auto vm) {
+        return for_value<2, 4, 6, 12, 10, 20>(p.utt, [&](auto utt) {
+          constexpr int UM = decltype(um)::value, VM = decltype(vm)::value, UTT = decltype(utt)::value;
+          p.kern = k_gemm_tn2<UM, VM, UTT, 1, 128>;
+          if constexpr (UTT >= 4 && UTT <= 12)
+            if (wide) p.kern = k_gemm_tn2<UM, VM, UTT, 2, 64>;
+          return 0;
+        });
+      }))
+    return false;
+  const int vw = 64 * p.vtt, uw = 16 * p.utt;
+  p.vt = (a.NV + vw - 1) / vw, p.uz = (a.NU + uw - 1) / uw;
+  p.lds = (size_t)(vw + uw) * (p.slab_rows + 8) * sizeof(bf16_t) + (size_t)3 * (vw + uw) * sizeof(float);
+  const long tiles = (long)p.vt * p.uz;
+  long want = (long)num_cus() * resident_per_cu(p.kern, 256, p.lds) / tiles;   // one round of resident workgroups
+  if (want > a.M / (2 * p.slab_rows)) want = a.M / (2 * p.slab_rows);          // at least two slabs per workgroup
+  if (want > tn_ws_cap(a)) want = tn_ws_cap(a);
+  p.xcd = want >= 8;                 // fewer chunks than XCDs: plain order
+  if (p.xcd) want = want / 8 * 8;    // equal work per XCD
+  tn_split(a.M, want, 0, 1, p.chunks, p.rows);
+  p.grid = (unsigned)((p.xcd ? (p.chunks + 7) / 8 * 8 : p.chunks) * tiles);
+  return true;
+}
+static int tn_slab_launch(const TnSlabPlan& p, const TnArgs& a) {
+  hipLaunchKernelGGL(p.kern, dim3(p.grid), dim3(256), p.lds, a.st, a.U, a.NU, a.V, a.NV, a.out, a.si, a.sj, a.M, p.rows, (int)p.chunks, p.vt,
+                     p.uz, p.xcd, p.chunks > 1 ? a.ws : nullptr);
+  return tn_finish("gemm_tn2", a, p.chunks);
+}
+
+// ---- generic: fp32 storage, every shape and supported prologue pair (k_gemm_tn); false: for_pair has set the error
+using TnGenericKernel = decltype(&k_gemm_tn<float, PRO_NONE, PRO_NONE>);
+struct TnGenericPlan { TnGenericKernel kern; int vt, uz; long chunks, rows; };
+static bool tn_generic_plan(const TnArgs& a, TnGenericPlan& p) {
+  if (for_pair(a.umode, a.vmode, [&](auto um, auto vm) { p.kern = k_gemm_tn<float, decltype(um)::value, decltype(vm)::value>; return 0; }))
+    return false;
+  p.vt = (a.NV + 63) / 64, p.uz = (a.NU + 16 * UT_MAX - 1) / (16 * UT_MAX);
+  const long tiles = (long)p.vt * p.uz;
+  long want = (1024 + tiles - 1) / tiles;   // enough row chunks to fill the chip, but at least 8 slabs of 32 rows per workgroup
+  if (want > tn_ws_cap(a)) want = tn_ws_cap(a);
+  tn_split(a.M, want, 8 * TN_ROWS, TN_ROWS, p.chunks, p.rows);
+  return true;
+}
+static int tn_generic_launch(const TnGenericPlan& p, const TnArgs& a) {
+  hipLaunchKernelGGL(p.kern, dim3((unsigned)p.chunks, p.vt, p.uz), dim3(256), 0, a.st, a.U, a.NU, a.V, a.NV, a.out, a.si, a.sj, a.M, p.rows,
+                     p.chunks > 1 ? a.ws : nullptr);
+  return tn_finish("gemm_tn", a, p.chunks);
+}
+
+static int launch_tn(const TnArgs& a, int dtype) {
+  TnDmaPlan dma; TnSlabPlan slab; TnGenericPlan generic;
+  if (dtype == DT_BF16 && tn_dma_plan(a, dma)) return tn_dma_launch(dma, a);
+  if (dtype == DT_BF16 && tn_slab_plan(a, slab)) return tn_slab_launch(slab, a);
+  if (dtype == DT_F32 && tn_generic_plan(a, generic)) return tn_generic_launch(generic, a);
+  return 1;   // no kernel for this prologue pair: the error is for_pair's
 }
 
 }  // namespace atomnas
-
-#if TN_TIMING
-extern "C" int atomnas_debug_tn_timing(unsigned long long* out8, int reset) {
-  unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipDeviceSynchronize() != hipSuccess) return 1;
-  if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(atomnas::g_tn_timing), sizeof(z)) != hipSuccess) return 1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(atomnas::g_tn_timing), z, sizeof(z)) != hipSuccess) return 1;
-  return 0;
-}
-#endif
 
 using namespace atomnas;
 
@@ -855,8 +768,5 @@ extern "C" int atomnas_pw_gemm_tn(int u_mode, const void* u, int ldu, long u_ss,
   ATOMNAS_REQUIRE((u_ss == 0 || u_ss >= M * 16) && (v_ss == 0 || v_ss >= M * 16), "pw_gemm_tn: slab stride smaller than M*16");
   if (check_operand("pw_gemm_tn(U)", U, u_mode, NU)) return 1;
   if (check_operand("pw_gemm_tn(V)", V, v_mode, NV)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_F32) return launch_tn<float>(u_mode, U, NU, v_mode, V, NV, out, si, sj, M, ws, ws_floats, st);
-  return launch_tn<bf16_t>(u_mode, U, NU, v_mode, V, NV, out, si, sj, M, ws, ws_floats, st);
+  return launch_tn(TnArgs{u_mode, U, NU, v_mode, V, NV, out, si, sj, M, ws, ws_floats, (hipStream_t)stream}, dtype);
 }
-

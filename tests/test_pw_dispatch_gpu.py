@@ -62,8 +62,8 @@ def whole_chip(gpu_lib):
         pytest.skip("the table is for a whole MI355X (256 CUs): the grids are sized from the CU count, this device has %d" % cus)
 
 
-def _assert_rows(section, got, keys):
-    rows = TABLE[section]
+def _assert_rows(section, got, keys, table=TABLE):
+    rows = table[section]
     assert len(got) == len(rows)
     bad = [(i, {k: v for k, v in r.items() if len(str(v)) < 40}, [k for k, g in zip(keys, a) if r[k] != g])
            for i, (r, a) in enumerate(zip(rows, got)) if [r[k] for k in keys] != list(a)]

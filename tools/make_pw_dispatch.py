@@ -222,11 +222,12 @@ def emit(mode):
     return out
 
 
-def in_child(mode):
-    """emit(mode) of a fresh interpreter: the caller's ATOMNAS_NT_* / ATOMNAS_XB_* switches are stripped, only the mode's are set"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith(("ATOMNAS_NT_", "ATOMNAS_XB_"))}
-    env.update(MODES[mode])
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--emit", mode], env=env, capture_output=True, text=True, timeout=600)
+def in_child(mode, script=__file__, modes=MODES, strip=("ATOMNAS_NT_", "ATOMNAS_XB_")):
+    """emit(mode) of a fresh interpreter: the caller's ATOMNAS_NT_* / ATOMNAS_XB_* switches are stripped, only the mode's are set
+    (tools/make_tn_dispatch.py passes its own script, modes and prefixes)"""
+    env = {k: v for k, v in os.environ.items() if not k.startswith(strip)}
+    env.update(modes[mode])
+    r = subprocess.run([sys.executable, os.path.abspath(script), "--emit", mode], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
 

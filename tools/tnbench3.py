@@ -1,5 +1,5 @@
 """Micro-benchmark of the single-stream weight-gradient GEMMs of the late stages (atomnas_pw_gemm_tn, (NONE, BNRELU) prologue pair).
-    python tools/tnbench3.py      env: ATOMNAS_TN_DMA=0/1, ATOMNAS_TN3_DEPTH=2/3/4, ATOMNAS_TN_TR=0/1"""
+    python tools/tnbench3.py      env: ATOMNAS_TN_DMA=0 (k_gemm_tn2 instead of the LDS-DMA kernel k_gemm_tn3; the only switch left)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from atomnas_amd import ops
