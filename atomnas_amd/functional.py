@@ -134,20 +134,16 @@ def bn_backward_coeffs(bn, st, stats2, count, dev):
 
 
 # ---------------------------------------------------------------------------------------------- atomic block
-_FUSED_PROJECT_BWD = bool(int(os.environ.get("ATOMNAS_FUSED_PROJECT_BWD", "1")))   # experiment switch (A/B against the two-GEMM form)
-# widest block output that takes the fused kernel.  The library covers oup <= 96, but the 80/96-wide instances hold 223 VGPR + 96 AGPR
-# (one wave per SIMD) and measured slower than the two-GEMM form on the 14x14 stages: 36.53 vs 36.30 ms/step (r03, bs256 bf16).
-_FUSED_PROJECT_BWD_MAXOUP = int(os.environ.get("ATOMNAS_FUSED_PROJECT_BWD_MAXOUP", "48"))
-_FUSED_EXPAND_BWD = int(os.environ.get("ATOMNAS_FUSED_EXPAND_BWD", "48"))   # experiment switch: widest inp that takes the fused kernel (0: never)
-# Expand backward without the raw expand output E (csrc/xbwd.hip): with dE = c1*h + c2*E + c3 and E = x We^T the c2 / c3 terms are
-# inp x inp sized corrections (Gram matrix of x), so the wide GEMMs read h only.  Widest block input that takes this form (0: never;
-# bf16 only).  48 = stages 1-3 with the streaming kernel k_expand_bwd_s (same-box A/Bs: 31.15 -> 30.20 ms for inp <= 24, -> 30.11 with
-# the per-segment launches of 40 -> 720; the 31.41 of profiles/r04_expand_bwd_noe_ab.txt for 48 predates that kernel).
-_EXPAND_BWD_NOE = int(os.environ.get("ATOMNAS_EXPAND_BWD_NOE", "48"))
-_PLAIN_HIDDEN = bool(int(os.environ.get("ATOMNAS_PLAIN_HIDDEN", "0")))
 # fused block (AtomNAS+): one weight-gradient GEMM per layer into a padded scratch + fold jobs (0: one GEMM per kernel-size segment)
 _FUSED_WG_BATCH = bool(int(os.environ.get("ATOMNAS_FUSED_WG_BATCH", "1")))
-_DP_TENSOR = bool(int(os.environ.get("ATOMNAS_DP_TENSOR", "1")))   # experiment switch: 0 = the BatchNorm-backward prologue in every GEMM tile
+_CHECK_LOSS_SEED = bool(int(os.environ.get("ATOMNAS_CHECK_LOSS_SEED", "0")))   # experiment switch (same-box A/B of the two layouts)
+# widest block output that takes the fused projection backward.  The library covers oup <= 96, but the 80/96-wide instances hold 223 VGPR +
+# 96 AGPR (one wave per SIMD) and measured slower than the two-GEMM form on the 14x14 stages: 36.53 vs 36.30 ms/step (r03, bs256 bf16)
+PROJECT_BWD_FUSED_MAX_OUP = 48
+# widest block input that takes the expand backward without the raw expand output E (csrc/xbwd.hip; atomnas_gram itself serves
+# inp <= 64).  48 = stages 1-3 with the streaming kernel k_expand_bwd_s (same-box A/Bs: 31.15 -> 30.20 ms for inp <= 24, -> 30.11 with
+# the per-segment launches of 40 -> 720; the 31.41 of profiles/r04_expand_bwd_noe_ab.txt for 48 predates that kernel)
+EXPAND_BWD_NOE_MAX_INP = 48
 TAIL_TAP = None   # set to a list by tests to receive the dropout keep mask of every tail forward
 # set to a list by tests to receive, for every activation the forward applies, (kind, plan, raw tensor, scale, shift): the pre-activation
 # is raw * scale + shift per channel -- what a test needs to compare ReLU masks with the oracle's (tests/test_block_gpu.py)
@@ -178,77 +174,141 @@ def _stap(pl, **tensors):
                     STEP_TAP.append(("%s.%s%d" % (pl.name, what, q + 1), u))
             else:
                 STEP_TAP.append(("%s.%s" % (pl.name, what), t))
-_CHECK_LOSS_SEED = bool(int(os.environ.get("ATOMNAS_CHECK_LOSS_SEED", "0")))   # experiment switch (same-box A/B of the two layouts)
 
 
 def _hidden(pl, M, C, T, dev):
     """hidden tensor of a block: slab-major (ops.Slab) for expanding blocks, plain [M, C] for the narrow non-expanding one"""
-    return Slab(M, C, T, dev) if (pl.expand and not _PLAIN_HIDDEN) else torch.empty(M, C, dtype=T, device=dev)
+    return Slab(M, C, T, dev) if pl.expand else torch.empty(M, C, dtype=T, device=dev)
 
 
 def _seg(t, o):
     return t.seg(o) if isinstance(t, Slab) else (t[:, o:] if o else t)
 
 
+def _fwd_stats(st, off=0, mode=True):
+    """statistics keywords of a forward producer in front of a BatchNorm (st None: running statistics, nothing is written).
+    off: branch segment of a fused hidden tensor; mode=False: a producer without a statistics mode (the depthwise forward)"""
+    kw = dict(stats=st.at(off), stat_rows=st.rows) if st is not None else dict(stats=None, stat_rows=None)
+    if mode:
+        kw["stat_mode"] = STAT_SQ if st is not None else 0
+    return kw
+
+
+def _pro(side, t, mode=PRO_NONE, t2=None, coeffs=(), relu=0, off=0):
+    """A GEMM operand, described once as the tuple (t, mode, t2, coeffs, relu) -- t as it is, act(c1*t + c2) (PRO_BNRELU) or
+    c1*t + c2*t2 + c3 (PRO_BNBWD) -- seen from hidden channel `off` on.  -> its keywords of ops.gemm_nt (side "a") or ops.gemm_tn
+    ("u", "v"): <side>, <side>_mode, <side>2, <side>c1..3, <side>_relu"""
+    kw = {side: _seg(t, off), side + "_mode": mode, side + "2": None if t2 is None else _seg(t2, off), side + "_relu": relu}
+    kw.update(("%sc%d" % (side, q + 1), c[off:]) for q, c in enumerate(coeffs))
+    return kw
+
+
+def _wg_jobs(pl, layer):
+    """Launches of a block's "project" ([oup, hidden]) or "expand" ([hidden, inp]) weight gradient -> ([(segment offset, width,
+    destination, its pitch)], (first fold job, number of fold jobs) to submit afterwards).  A fused block's weights are contiguous
+    over the un-padded branch widths: ONE launch into the layer's padded scratch matrix + folds, or one launch per branch segment."""
+    project = layer == "project"
+    if not pl.fused:
+        return [(0, pl.HT, pl.Wp_grad if project else pl.We_grad, pl.HT if project else pl.inp)], (0, 0)
+    if _FUSED_WG_BATCH:
+        off, n = (pl.Wp_scratch_off, pl.oup * pl.HT) if project else (pl.We_scratch_off, pl.HT * pl.inp)
+        fold = (pl.fold_first, pl.fold_np) if project else (pl.fold_first + pl.fold_np, pl.fold_ne)
+        return [(0, pl.HT, pl.mgr.FW[off:off + n], pl.HT if project else pl.inp)], fold
+    grad, row, pitch = (pl.Wp_grad, 1, pl.total) if project else (pl.We_grad, pl.inp, pl.inp)
+    return [(sg, h, grad[st * row:], pitch) for sg, st, h in zip(pl.seg, pl.start, pl.hid)], (0, 0)
+
+
+def _se_forward(D, scale, shift, act, S, cmap, w1p, b1, w2t, b2p, se_act, hid, N, HW, HT):
+    """SqueezeAndExcitation (models/mobilenet_base.py:109-112) on A = act(scale * D + shift): squeeze -> two tiny dense layers
+    (packed over the padded channel layout) -> gate; S = gate * A.  -> what the backward needs: pooled, gate, hpre"""
+    dev = S.device
+    sv = dict(pooled=_f32(N * HT, dev).view(N, HT), gate=_f32(N * HT, dev).view(N, HT), hpre=_f32(N * hid, dev).view(N, hid))
+    parts = ops.se_pool_parts(N, HW, HT)
+    pooled_parts = _f32(parts * N * HT, dev).view(parts, N, HT)
+    ops.se_squeeze(D, scale, shift, act, pooled_parts, N, HW, HT)
+    ops.se_mlp_fwd(pooled_parts, sv["pooled"], cmap, w1p, b1, w2t, b2p, se_act, sv["hpre"], sv["gate"], N, HT, hid)
+    ops.se_scale(D, scale, shift, act, sv["gate"], S, N * HW, HW, HT)
+    return sv
+
+
+def _se_backward(dS, D, scale, shift, act, sv, cmap, w1p, w2t, se_act, hid, dw1, db1, dw2, db2, total, g, st2, N, HW, HT):
+    """dS = dL/dS -> g = dL/dD' (D' = scale * D + shift) with its BatchNorm-backward statistics in st2: back through the gate
+    (dense-layer gradients accumulate into dw1 / db1 / dw2 / db2, contiguous over `total` channels) and the activation"""
+    dev = g.device
+    dz2, dpooled = (_f32(N * HT, dev).view(N, HT) for _ in range(2))
+    parts = ops.se_pool_parts(N, HW, HT)
+    dgate = _f32(parts * N * HT, dev).view(parts, N, HT)
+    dz1 = _f32(N * hid, dev).view(N, hid)
+    ops.se_bwd_gate(dS, D, scale, shift, act, sv["gate"], sv["pooled"], cmap, w1p, w2t, sv["hpre"], dgate, dz2, dz1, dpooled, dw1, db1, dw2,
+                    db2, N, HW, HT, total, hid, se_act=se_act)
+    ops.se_bwd_apply(dS, D, scale, shift, act, sv["gate"], dpooled, g, st2.t, N * HW, HW, HT, stat_rows=st2.rows)
+
+
 def block_forward(pl, x2d, N, H, W, need_grad):
     """InvertedResidualChannels.forward on arena views.  Returns (out2d, saved) -- saved is None when need_grad is False."""
     dev, T = x2d.device, x2d.dtype
-    M = N * H * W
-    s = pl.stride
+    HT, s, act = pl.HT, pl.stride, pl.act
     Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    M2 = N * Ho * Wo
-    HT = pl.HT
-    act = pl.act
-    sv = {}
+    M, M2 = N * H * W, N * Ho * Wo
     if pl.expand:
-        bs = bn_uses_batch_stats(pl.bne)
         E = _hidden(pl, M, HT, T, dev)
-        stE = _stats(HT, dev, pl.bne["mgr"]) if bs else None
-        ops.gemm_nt(x2d, pl.We_pack, E, M, HT, pl.inp, stats=stE.t if bs else None, stat_mode=STAT_SQ if bs else 0,
-                    stat_rows=stE.rows if bs else None)
+        stE = _stats(HT, dev, pl.bne["mgr"]) if bn_uses_batch_stats(pl.bne) else None
+        ops.gemm_nt(x2d, pl.We_pack, E, M, HT, pl.inp, **_fwd_stats(stE))
         bE = bn_forward_coeffs(pl.bne, stE, M, dev)
         _tap("expand", pl, E, bE)
     else:
         E, bE = x2d, None
-    bsd = bn_uses_batch_stats(pl.bnd)
     D = _hidden(pl, M2, HT, T, dev)
-    stD = _stats(HT, dev, pl.bnd["mgr"]) if bsd else None
+    stD = _stats(HT, dev, pl.bnd["mgr"]) if bn_uses_batch_stats(pl.bnd) else None
     for i in range(pl.nb):
         o, c = pl.seg[i], pl.segpad(pl.hid[i])
-        xin = _seg(E, o) if pl.expand else E
-        ops.dwconv_fwd(xin, bE.scale[o:] if bE else None, bE.shift[o:] if bE else None, act if bE else 0, pl.taps[i], _seg(D, o),
-                       stD.at(o) if bsd else None, HT, N, H, W, c, pl.ks[i], s, stat_rows=stD.rows if bsd else None)
+        ops.dwconv_fwd(_seg(E, o), bE.scale[o:] if bE else None, bE.shift[o:] if bE else None, act if bE else 0, pl.taps[i], _seg(D, o),
+                       stat_ld=HT, N=N, H=H, W=W, C=c, k=pl.ks[i], stride=s, **_fwd_stats(stD, o, mode=False))
     bD = bn_forward_coeffs(pl.bnd, stD, M2, dev)
     _tap("dw", pl, D, bD)
-    bsp = bn_uses_batch_stats(pl.bnp)
     Pr = torch.empty(M2, pl.oup, dtype=T, device=dev)
-    stP = _stats(pl.oup, dev, pl.bnp["mgr"]) if bsp else None
-    se = None
+    stP = _stats(pl.oup, dev, pl.bnp["mgr"]) if bn_uses_batch_stats(pl.bnp) else None
+    # the projection's operand A: the activated depthwise output act(bn(D)) as a prologue of D, or gated by the SE as a tensor S
+    se, A = None, (D, PRO_BNRELU, None, (bD.scale, bD.shift), int(act))
     if pl.se:
-        # SqueezeAndExcitation (models/mobilenet_base.py:109-112) on the activated depthwise output A = act(bn(D)):
-        # squeeze -> two tiny dense layers -> gate; the gated tensor S is the projection's operand
-        HWo = Ho * Wo
-        se = dict(pooled=_f32(N * HT, dev).view(N, HT), gate=_f32(N * HT, dev).view(N, HT), hpre=_f32(N * pl.se_hid, dev).view(N, pl.se_hid))
-        parts = ops.se_pool_parts(N, HWo, HT)
-        pooled_parts = _f32(parts * N * HT, dev).view(parts, N, HT)
-        ops.se_squeeze(D, bD.scale, bD.shift, int(act), pooled_parts, N, HWo, HT)
-        ops.se_mlp_fwd(pooled_parts, se["pooled"], pl.cmap, pl.se_w1p, pl.se_b1, pl.se_w2t, pl.se_b2p, pl.se_act, se["hpre"], se["gate"], N, HT, pl.se_hid)
-        Sx = _hidden(pl, M2, HT, T, dev)
-        ops.se_scale(D, bD.scale, bD.shift, int(act), se["gate"], Sx, M2, HWo, HT)
-        se["S"] = Sx
-        ops.gemm_nt(Sx, pl.Wp_pack, Pr, M2, pl.oup, HT, stats=stP.t if bsp else None, stat_mode=STAT_SQ if bsp else 0,
-                    stat_rows=stP.rows if bsp else None)
-    else:
-        ops.gemm_nt(D, pl.Wp_pack, Pr, M2, pl.oup, HT, a_mode=PRO_BNRELU, ac1=bD.scale, ac2=bD.shift, a_relu=int(act),
-                    stats=stP.t if bsp else None, stat_mode=STAT_SQ if bsp else 0, stat_rows=stP.rows if bsp else None)
+        A = (_hidden(pl, M2, HT, T, dev),)
+        se = _se_forward(D, bD.scale, bD.shift, int(act), A[0], pl.cmap, pl.se_w1p, pl.se_b1, pl.se_w2t, pl.se_b2p, pl.se_act, pl.se_hid,
+                         N, Ho * Wo, HT)
+    ops.gemm_nt(wp=pl.Wp_pack, c=Pr, M=M2, N=pl.oup, K=HT, **_pro("a", *A), **_fwd_stats(stP))
     bP = bn_forward_coeffs(pl.bnp, stP, M2, dev)
     out = torch.empty(M2, pl.oup, dtype=T, device=dev)
     ops.bn_apply(Pr, bP.scale, bP.shift, False, x2d if pl.res else None, out, M2, pl.oup)
     _stap(pl, E=E if pl.expand else None, bne=bE, D=D, bnd=bD, P=Pr, bnp=bP, out=out)
-    if need_grad:
-        sv = dict(x=x2d, E=E, D=D, P=Pr, bE=bE, bD=bD, bP=bP, dims=(N, H, W, Ho, Wo), se=se)
-        return out, sv
-    return out, None
+    return out, dict(x=x2d, E=E, D=D, P=Pr, bE=bE, bD=bD, bP=bP, dims=(N, H, W, Ho, Wo), se=se, A=A) if need_grad else None
+
+
+def project_bwd_form(pl, T, M2, G, D, g, stat_rows):
+    """-> "fused" | "dp" | "prologue": the form a block's projection backward takes (G, D, g: its tensors, for their layouts)"""
+    # "fused": weight and input gradient from ONE pass over D (atomnas_project_bwd on the materialised dP).  Early stages: plain blocks
+    # (an SE needs dL/dS between the two gradients, a fused block's weight is not [oup, HT]) up to the widest output at which the
+    # fused kernel wins, where the library has an instance for the widths and serves the layouts
+    if (pl.expand and not pl.fused and not pl.se and pl.oup <= PROJECT_BWD_FUSED_MAX_OUP and ops.project_bwd_supported(pl.oup, pl.HT, T)
+            and ops.project_bwd_dp_supported(M2, pl.oup, pl.HT, G, D, g, stat_rows)):
+        return "fused"
+    # "dp": dP = p1*G + p2*P + p3 materialised once, two GEMMs read it without a prologue.  Late stages (oup >= 80: every row of dP
+    # feeds 23..54 GEMM tiles): dP is a few MB, and the input-gradient GEMM takes the streaming kernel (k_gemm_nt_st), measured
+    # 84 / 102 / 74 us against 158 / 198 / 208 us with the prologue (14x14 80 / 96 wide, 7x7).  bf16 rows of a multiple of 8 channels;
+    # else (fp32 storage) "prologue": two GEMMs with the BatchNorm backward of (G, P) in every tile
+    return "dp" if T == torch.bfloat16 and pl.oup % 8 == 0 else "prologue"
+
+
+def expand_bwd_form(pl, T, x2d, h):
+    """-> "noe_fused" | "noe_segments" | "noe_gemms" | "e": the form a block's expand backward takes (x2d, h: its tensors, for their layouts)"""
+    # "e": two GEMMs with the BatchNorm backward of (h, E) as their prologue.  The forms without the raw expand output E serve bf16
+    # plain blocks up to the widest input at which they win; atomnas_gram reads rows of a multiple of 8 channels and pitch
+    if not (T == torch.bfloat16 and not pl.fused and pl.inp <= EXPAND_BWD_NOE_MAX_INP and pl.inp % 8 == 0 and x2d.stride(0) % 8 == 0):
+        return "e"
+    if ops.expand_bwd_supported(pl.inp, pl.HT, T):   # both gradients from ONE pass over h: the accumulators of the hidden width fit
+        return "noe_fused"
+    # 40 -> 720: those of one branch segment (240 channels) do -- the same kernel once per segment; else three GEMMs
+    if pl.nb > 1 and isinstance(h, Slab) and all(ops.expand_bwd_supported(pl.inp, pl.segpad(hh), T) for hh in pl.hid):
+        return "noe_segments"
+    return "noe_gemms"
 
 
 def block_backward(pl, sv, G):
@@ -256,118 +316,81 @@ def block_backward(pl, sv, G):
     dev, T = G.device, G.dtype
     N, H, W, Ho, Wo = sv["dims"]
     M, M2 = N * H * W, N * Ho * Wo
-    HT, s, act = pl.HT, pl.stride, pl.act
-    x2d, E, D, Pr, bE, bD, bP = sv["x"], sv["E"], sv["D"], sv["P"], sv["bE"], sv["bD"], sv["bP"]
-    # shared pw_bn backward: statistics pass over (G, P), then coefficients
+    HT, s = pl.HT, pl.stride
+    x2d, E, D, bE = sv["x"], sv["E"], sv["D"], sv["bE"]
+    # pw_bn backward: statistics pass over (G, P), then coefficients
     st2P = _stats(pl.oup, dev, pl.bnp["mgr"])
-    ops.act_bwd_stats(G, Pr, None, None, False, None, st2P.t, M2, pl.oup, stat_rows=st2P.rows)
-    p1, p2, p3 = bn_backward_coeffs(pl.bnp, bP, st2P, M2, dev)
-    se = sv.get("se")
-    # projection weight gradient: dWp[n][k] = sum_m dP[m][n] * A'[m][k], A' = act(bn(D)) (gated by the SE when there is one).
-    # The fused block's projection weight is one contiguous [oup, total] tensor: one launch per branch segment.
-    wp_jobs = ([(sg, h, pl.Wp_grad[stt:], pl.total) for sg, stt, h in zip(pl.seg, pl.start, pl.hid)] if pl.fused
-               else [(0, HT, pl.Wp_grad, HT)])
-    # early stages (oup <= 48, no SE): the weight gradient rides in the input-gradient kernel below (one pass over D), which takes the
-    # differentiated pw_bn output dP as a tensor
+    ops.act_bwd_stats(G, sv["P"], None, None, False, None, st2P.t, M2, pl.oup, stat_rows=st2P.rows)
+    p = bn_backward_coeffs(pl.bnp, sv["bP"], st2P, M2, dev)
+    # projection backward by form: g = gradient wrt the dw_bn output, with the dw_bn backward statistics
     g = _hidden(pl, M2, HT, T, dev)
     st2D = _stats(HT, dev, pl.bnd["mgr"])
-    fused_pb = (_FUSED_PROJECT_BWD and _DP_TENSOR and se is None and not pl.fused and pl.expand and pl.oup <= _FUSED_PROJECT_BWD_MAXOUP
-                and ops.project_bwd_supported(pl.oup, HT, T) and ops.project_bwd_dp_supported(M2, pl.oup, HT, G, D, g, st2D.rows))
-    # late stages (oup >= 80: every row of dP feeds 23..54 GEMM tiles): the differentiated pw_bn output dP = p1*G + p2*P + p3 is
-    # materialised once (a few MB) and the GEMMs below read it without a prologue -- the input-gradient GEMM then takes the streaming
-    # kernel (k_gemm_nt_st), measured 84 / 102 / 74 us against 158 / 198 / 208 us with the prologue (14x14 80 / 96 wide, 7x7)
-    dP = None
-    if _DP_TENSOR and not fused_pb and T == torch.bfloat16 and pl.oup % 8 == 0:
-        dP = torch.empty(M2, pl.oup, dtype=T, device=dev)
-        ops.bnbwd_apply(G, Pr, p1, p2, p3, dP, M2, pl.oup)
-    if pl.fused and _FUSED_WG_BATCH:
-        # ONE launch over the padded width into the layer's scratch matrix, folded into the contiguous [oup, total] gradient per segment
-        mgr = pl.mgr
-        wp_jobs = [(0, HT, mgr.FW[pl.Wp_scratch_off:pl.Wp_scratch_off + pl.oup * HT], HT)]
-    for sg, nv, out, si in ([] if fused_pb else wp_jobs):
-        if se is not None and dP is not None:
-            ops.gemm_tn(dP, pl.oup, _seg(se["S"], sg), nv, out, si, 1, M2)
-        elif se is not None:
-            ops.gemm_tn(G, pl.oup, _seg(se["S"], sg), nv, out, si, 1, M2, u_mode=PRO_BNBWD, u2=Pr, uc1=p1, uc2=p2, uc3=p3)
-        elif dP is not None:
-            ops.gemm_tn(dP, pl.oup, _seg(D, sg), nv, out, si, 1, M2, v_mode=PRO_BNRELU, vc1=bD.scale[sg:], vc2=bD.shift[sg:],
-                        v_relu=int(act))
-        else:
-            ops.gemm_tn(G, pl.oup, _seg(D, sg), nv, out, si, 1, M2, u_mode=PRO_BNBWD, u2=Pr, uc1=p1, uc2=p2, uc3=p3, v_mode=PRO_BNRELU,
-                        vc1=bD.scale[sg:], vc2=bD.shift[sg:], v_relu=int(act))
-    if pl.fused and _FUSED_WG_BATCH:
-        ops.fold_jobs(pl.mgr, pl.fold_first, pl.fold_np)
+    dP = _project_backward(pl, project_bwd_form(pl, T, M2, G, D, g, st2D.rows), sv, G, p, g, st2D)
+    d1, d2, d3 = d = bn_backward_coeffs(pl.bnd, sv["bD"], st2D, M2, dev)
+    # depthwise backward per branch
+    h = _hidden(pl, M, HT if pl.expand else pl.inp, T, dev)
+    if pl.expand:
+        st2E = _stats(HT, dev, pl.bne["mgr"])
+        for i in range(pl.nb):
+            o, c = pl.seg[i], pl.segpad(pl.hid[i])
+            ops.dwconv_bwd(_seg(g, o), _seg(D, o), d1[o:], d2[o:], d3[o:], _seg(E, o), bE.scale[o:], bE.shift[o:], pl.act, pl.taps[i],
+                           _seg(h, o), pl.Wd_grad[i], st2E.at(o), HT, N, H, W, c, pl.ks[i], s, stat_rows=st2E.rows)
+    elif pl.nb > 1:
+        raise NotImplementedError("non-expanding block with more than one branch")
+    else:
+        ops.dwconv_bwd(g, D, d1, d2, d3, E, None, None, 0, pl.taps[0], h, pl.Wd_grad[0], None, 0, N, H, W, pl.segpad(pl.hid[0]), pl.ks[0], s)
+    _stap(pl, p=p, dP=dP, g=g, d=d, h=h)
+    if not pl.expand:
+        return h + G if pl.res else h
+    e = bn_backward_coeffs(pl.bne, bE, st2E, M, dev)
+    _stap(pl, e=e)
+    # expand backward by form (+ residual branch)
+    Gx = torch.empty(M, pl.inp, dtype=T, device=dev)
+    res = G if pl.res else None
+    form = expand_bwd_form(pl, T, x2d, h)
+    if form != "e":
+        return _expand_backward_noe(pl, form, x2d, h, e, res, Gx, M)
+    # dE = e1*h + e2*E + e3 as the GEMMs' prologue.  Weight gradient dWe[n][k] = sum_m dE[m][n] * x[m][k] (written transposed:
+    # out[i=k][j=n] -> dWe[n*inp + k]), then the input gradient
+    dE = (h, PRO_BNBWD, E, e)
+    jobs, fold = _wg_jobs(pl, "expand")
+    for sg, nv, out, pitch in jobs:
+        ops.gemm_tn(u=x2d, NU=pl.inp, NV=nv, out=out, si=1, sj=pitch, M=M, **_pro("v", *dE, off=sg))
+    ops.fold_jobs(pl.mgr, *fold)
+    ops.gemm_nt(wp=pl.WeT_pack, c=Gx, M=M, N=pl.inp, K=HT, add=res, **_pro("a", *dE))
+    return Gx
+
+
+def _project_backward(pl, form, sv, G, p, g, st2D):
+    """Projection backward in the form project_bwd_form chose: dWp[n][k] = sum_m dP[m][n] * A[m][k] into the gradient arena; g = dP Wp
+    back through the SE gate / masked by the depthwise activation, dw_bn backward statistics in st2D.  -> dP tensor of the "dp" form"""
+    N, _, _, Ho, Wo = sv["dims"]
+    M2, HT, act = N * Ho * Wo, pl.HT, int(pl.act)
+    D, Pr, bD, se = sv["D"], sv["P"], sv["bD"], sv["se"]
+    if form == "prologue":
+        dP, dPop = None, (G, PRO_BNBWD, Pr, p)
+    else:   # dP once: a narrow tensor that the kernels below stream without a prologue
+        dP = torch.empty(M2, pl.oup, dtype=G.dtype, device=G.device)
+        ops.bnbwd_apply(G, Pr, *p, dP, M2, pl.oup)
+        dPop = (dP,)
+    if form == "fused":
+        ops.project_bwd(dP, pl.WpT_pack, D, bD.scale, bD.shift, act, g, st2D.t, pl.Wp_grad, HT, 1, M2, pl.oup, HT, stat_rows=st2D.rows)
+        return None
+    jobs, fold = _wg_jobs(pl, "project")
+    for sg, nv, out, pitch in jobs:
+        ops.gemm_tn(NU=pl.oup, NV=nv, out=out, si=pitch, sj=1, M=M2, **_pro("u", *dPop), **_pro("v", *sv["A"], off=sg))
+    ops.fold_jobs(pl.mgr, *fold)
     if se is not None:
         # gradient wrt the gated tensor, then back through the gate (models/mobilenet_base.py:109-112) and the activation
-        HWo = Ho * Wo
-        dS = _hidden(pl, M2, HT, T, dev)
-        if dP is not None:   # no prologue: the wide-output GEMM takes the streaming kernel (k_gemm_nt_st)
-            ops.gemm_nt(dP, pl.WpT_pack, dS, M2, HT, pl.oup)
-        else:
-            ops.gemm_nt(G, pl.WpT_pack, dS, M2, HT, pl.oup, a_mode=PRO_BNBWD, a2=Pr, ac1=p1, ac2=p2, ac3=p3)
-        nh = N * pl.se_hid
-        dz2, dpooled = (_f32(N * HT, dev).view(N, HT) for _ in range(2))
-        parts = ops.se_pool_parts(N, HWo, HT)
-        dgate = _f32(parts * N * HT, dev).view(parts, N, HT)
-        dz1 = _f32(nh, dev).view(N, pl.se_hid)
-        ops.se_bwd_gate(dS, D, bD.scale, bD.shift, int(act), se["gate"], se["pooled"], pl.cmap, pl.se_w1p, pl.se_w2t, se["hpre"], dgate, dz2,
-                        dz1, dpooled, pl.se_dw1, pl.se_db1, pl.se_dw2, pl.se_db2, N, HWo, HT, pl.total, pl.se_hid, se_act=pl.se_act)
-        ops.se_bwd_apply(dS, D, bD.scale, bD.shift, int(act), se["gate"], dpooled, g, st2D.t, M2, HWo, HT, stat_rows=st2D.rows)
-    elif fused_pb:
-        # dP once (a narrow tensor), then the streaming fused kernel: no prologue, nothing behind a branch
-        dPf = torch.empty(M2, pl.oup, dtype=T, device=dev)
-        ops.bnbwd_apply(G, Pr, p1, p2, p3, dPf, M2, pl.oup)
-        ops.project_bwd(dPf, pl.WpT_pack, D, bD.scale, bD.shift, int(act), g, st2D.t, pl.Wp_grad, HT, 1, M2, pl.oup, HT, stat_rows=st2D.rows)
+        dS = _hidden(pl, M2, HT, G.dtype, G.device)
+        ops.gemm_nt(wp=pl.WpT_pack, c=dS, M=M2, N=HT, K=pl.oup, **_pro("a", *dPop))
+        _se_backward(dS, D, bD.scale, bD.shift, act, se, pl.cmap, pl.se_w1p, pl.se_w2t, pl.se_act, pl.se_hid, pl.se_dw1, pl.se_db1,
+                     pl.se_dw2, pl.se_db2, pl.total, g, st2D, N, Ho * Wo, HT)
     else:
-        # projection input gradient, masked by the depthwise activation, with the depthwise-BN backward statistics
-        if dP is not None:
-            ops.gemm_nt(dP, pl.WpT_pack, g, M2, HT, pl.oup, z=D, zscale=bD.scale, zshift=bD.shift, mask=int(act), stats=st2D.t,
-                        stat_mode=STAT_Z, stat_rows=st2D.rows)
-        else:
-            ops.gemm_nt(G, pl.WpT_pack, g, M2, HT, pl.oup, a_mode=PRO_BNBWD, a2=Pr, ac1=p1, ac2=p2, ac3=p3, z=D, zscale=bD.scale,
-                        zshift=bD.shift, mask=int(act), stats=st2D.t, stat_mode=STAT_Z, stat_rows=st2D.rows)
-    d1, d2, d3 = bn_backward_coeffs(pl.bnd, bD, st2D, M2, dev)
-    # depthwise backward per branch
-    if pl.expand:
-        h = _hidden(pl, M, HT, T, dev)
-        st2E = _stats(HT, dev, pl.bne["mgr"])
-    else:
-        h = ops.zeros(M, pl.inp, dtype=T, device=dev) if pl.nb > 1 else torch.empty(M, pl.inp, dtype=T, device=dev)
-        st2E = None
-    for i in range(pl.nb):
-        o, c = pl.seg[i], pl.segpad(pl.hid[i])
-        if pl.expand:
-            ops.dwconv_bwd(_seg(g, o), _seg(D, o), d1[o:], d2[o:], d3[o:], _seg(E, o), bE.scale[o:], bE.shift[o:], act, pl.taps[i],
-                           _seg(h, o), pl.Wd_grad[i], st2E.at(o), HT, N, H, W, c, pl.ks[i], s, stat_rows=st2E.rows)
-        else:
-            if pl.nb > 1:
-                raise NotImplementedError("non-expanding block with more than one branch")
-            ops.dwconv_bwd(_seg(g, o), _seg(D, o), d1[o:], d2[o:], d3[o:], E, None, None, 0, pl.taps[i], h, pl.Wd_grad[i], None, 0, N, H,
-                           W, c, pl.ks[i], s)
-    _stap(pl, p=(p1, p2, p3), dP=dP, g=g, d=(d1, d2, d3), h=h)
-    if not pl.expand:
-        if pl.res:
-            h = h + G
-        return h
-    e1, e2, e3 = bn_backward_coeffs(pl.bne, bE, st2E, M, dev)
-    _stap(pl, e=(e1, e2, e3))
-    Gx = torch.empty(M, pl.inp, dtype=T, device=dev)
-    if (T == torch.bfloat16 and not pl.fused and pl.inp <= min(_EXPAND_BWD_NOE, 64) and pl.inp % 8 == 0 and x2d.stride(0) % 8 == 0):   # atomnas_gram: inp <= 64, row pitch % 8
-        return _expand_backward_noe(pl, x2d, h, e1, e2, e3, G if pl.res else None, Gx, M, HT, dev, T)
-    # expand weight gradient dWe[n][k] = sum_m dE[m][n] * x[m][k]  (written transposed: out[i=k][j=n] -> dWe[n*inp + k]); the
-    # fused block's expand weight is one contiguous [total, inp] tensor: one launch per branch segment
-    we_jobs = ([(sg, hh, pl.We_grad[stt * pl.inp:]) for sg, stt, hh in zip(pl.seg, pl.start, pl.hid)] if pl.fused
-               else [(0, HT, pl.We_grad)])
-    if pl.fused and _FUSED_WG_BATCH:
-        we_jobs = [(0, HT, pl.mgr.FW[pl.We_scratch_off:pl.We_scratch_off + HT * pl.inp])]
-    for sg, nv, out in we_jobs:
-        ops.gemm_tn(x2d, pl.inp, _seg(h, sg), nv, out, 1, pl.inp, M, v_mode=PRO_BNBWD, v2=_seg(E, sg), vc1=e1[sg:], vc2=e2[sg:],
-                    vc3=e3[sg:])
-    if pl.fused and _FUSED_WG_BATCH:
-        ops.fold_jobs(pl.mgr, pl.fold_first + pl.fold_np, pl.fold_ne)
-    # expand input gradient (+ residual branch)
-    ops.gemm_nt(h, pl.WeT_pack, Gx, M, pl.inp, HT, a_mode=PRO_BNBWD, a2=E, ac1=e1, ac2=e2, ac3=e3, add=G if pl.res else None)
-    return Gx
+        # projection input gradient, masked by the depthwise activation
+        ops.gemm_nt(wp=pl.WpT_pack, c=g, M=M2, N=HT, K=pl.oup, **_pro("a", *dPop), z=D, zscale=bD.scale, zshift=bD.shift, mask=act,
+                    stats=st2D.t, stat_mode=STAT_Z, stat_rows=st2D.rows)
+    return dP
 
 
 def _plan_buffer(pl, name, make):
@@ -379,14 +402,15 @@ def _plan_buffer(pl, name, make):
     return t
 
 
-def _expand_backward_noe(pl, x2d, h, e1, e2, e3, res, Gx, M, HT, dev, T):
+def _expand_backward_noe(pl, form, x2d, h, e, res, Gx, M):
     """Backward of the expand convolution from ONE hidden stream (models/mobilenet_base.py:316-320 backward).  With the BatchNorm
     backward dE = e1*h + e2*E + e3 and E = x We^T:
         dX  = (e1*h) We + x M + v (+ residual),        M = We^T diag(e2) We,  v = e3^T We
         dWe = (e1*h)^T x + diag(e2) We (X^T X) + e3 (sum x)^T
     The e2 / e3 terms are inp x inp sized (atomnas_gram + atomnas_xb_coeffs); the wide GEMMs read h alone (e1 as their scale
-    prologue), where the BNBWD-prologue forms read h and E."""
-    inp = pl.inp
+    prologue), where the BNBWD-prologue forms read h and E.  form: "noe_fused" | "noe_segments" | "noe_gemms" (expand_bwd_form)."""
+    dev, T, inp, HT = x2d.device, x2d.dtype, pl.inp, pl.HT
+    e1, e2, e3 = e
     gram = torch.empty(inp * inp, dtype=torch.float32, device=dev)
     sx = torch.empty(inp, dtype=torch.float32, device=dev)
     ops.gram(x2d, M, inp, gram, sx, ws=_plan_buffer(pl, "gram_ws", lambda: torch.empty(2048 * (inp * inp + inp), dtype=torch.float32, device=dev)))
@@ -394,40 +418,35 @@ def _expand_backward_noe(pl, x2d, h, e1, e2, e3, res, Gx, M, HT, dev, T):
     mp = _plan_buffer(pl, "xb_mp", lambda: ops.zeros((inp + 63) // 64 * 64, (inp + 31) // 32 * 32, dtype=T, device=dev))
     vb = torch.empty(pad8(inp), dtype=torch.float32, device=dev)
     ops.xb_coeffs(e2, e3, pl.We_pack, gram, sx, inp, HT, mp, vb, pl.We_grad)
-    if inp <= _FUSED_EXPAND_BWD and ops.expand_bwd_supported(inp, HT, T):
+    if form == "noe_fused":
         # one pass over h: both gradients, x M + v added inside the kernel
         ops.expand_bwd(h, e1, x2d, pl.WeT_pack, res, Gx, pl.We_grad, M, inp, HT, mp=mp, vb=vb)
-        return Gx
-    if (inp <= _FUSED_EXPAND_BWD and not pl.fused and pl.nb > 1 and isinstance(h, ops.Slab)
-            and all(ops.expand_bwd_supported(inp, pl.segpad(hh), T) for hh in pl.hid)):
-        # 40 -> 720: the accumulators of the whole hidden width do not fit, those of one branch segment (240 channels) do: one launch
-        # of the streaming kernel per segment; the input gradient accumulates through `add` (a launch reads and writes its own rows of
-        # Gx only), x M + v rides in the first launch
+    elif form == "noe_segments":
+        # one launch of the streaming kernel per segment; the input gradient accumulates through `add` (a launch reads and writes its
+        # own rows of Gx only), x M + v rides in the first launch
         for i in range(pl.nb):
             o, c = pl.seg[i], pl.segpad(pl.hid[i])
             ops.expand_bwd(_seg(h, o), e1[o:], x2d, pl.WeT_pack[:, o:], res if i == 0 else Gx, Gx, pl.We_grad[o * inp:], M, inp,
                            c, mp=mp if i == 0 else None, vb=vb if i == 0 else None)
-        return Gx
-    gx1 = torch.empty(M, inp, dtype=T, device=dev)
-    ops.gemm_nt(x2d, mp, gx1, M, inp, inp, bias=vb, add=res)
-    zeros = _plan_buffer(pl, "xb_zero%d" % e1.numel(), lambda: ops.zeros(e1.numel(), dtype=torch.float32, device=dev))
-    ops.gemm_tn(x2d, inp, h, HT, pl.We_grad, 1, inp, M, v_mode=PRO_BNRELU, vc1=e1, vc2=zeros, v_relu=0)
-    ops.gemm_nt(h, pl.WeT_pack, Gx, M, inp, HT, a_mode=PRO_BNRELU, ac1=e1, ac2=zeros, a_relu=0, add=gx1)
+    else:   # "noe_gemms"
+        gx1 = torch.empty(M, inp, dtype=T, device=dev)
+        ops.gemm_nt(x2d, mp, gx1, M, inp, inp, bias=vb, add=res)
+        zeros = _plan_buffer(pl, "xb_zero%d" % e1.numel(), lambda: ops.zeros(e1.numel(), dtype=torch.float32, device=dev))
+        e1h = (h, PRO_BNRELU, None, (e1, zeros))
+        ops.gemm_tn(u=x2d, NU=inp, NV=HT, out=pl.We_grad, si=1, sj=inp, M=M, **_pro("v", *e1h))
+        ops.gemm_nt(wp=pl.WeT_pack, c=Gx, M=M, N=inp, K=HT, add=gx1, **_pro("a", *e1h))
     return Gx
 
 
 class BlockFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, pl):
-        T = pl.mgr.compute_dtype
-        x2d, (N, H, W, C) = to_2d(x, T)
+        x2d, (N, H, W, C) = to_2d(x, pl.mgr.compute_dtype)
         if C != pl.inp:
             raise ValueError("block %s expects %d input channels, got %d" % (pl.name, pl.inp, C))
-        need = torch.is_grad_enabled() or ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         out, sv = block_forward(pl, x2d, N, H, W, True)
         ctx.pl, ctx.sv = pl, sv
-        Ho, Wo = sv["dims"][3], sv["dims"][4]
-        return to_4d(out, N, Ho, Wo, pl.oup)
+        return to_4d(out, N, *sv["dims"][3:], pl.oup)
 
     @staticmethod
     def backward(ctx, gout):
@@ -446,8 +465,7 @@ def run_block(pl, x, anchor):
         return x
     if torch.is_grad_enabled() and (x.requires_grad or anchor.requires_grad):
         return BlockFunction.apply(x, anchor, pl)
-    T = pl.mgr.compute_dtype
-    x2d, (N, H, W, C) = to_2d(x, T)
+    x2d, (N, H, W, C) = to_2d(x, pl.mgr.compute_dtype)
     out, _ = block_forward(pl, x2d, N, H, W, False)
     s = pl.stride
     return to_4d(out, N, (H - 1) // s + 1, (W - 1) // s + 1, pl.oup)
@@ -456,9 +474,8 @@ def run_block(pl, x, anchor):
 # ---------------------------------------------------------------------------------------------- stand-alone SqueezeAndExcitation
 class SEFunction(torch.autograd.Function):
     """SqueezeAndExcitation.forward (models/mobilenet_base.py:109-112) as a module call of its own: sigmoid(W2 act(W1 mean(x) + b1) + b2) * x
-    with the SE entry points the fused block uses (squeeze -> dense layers -> scale; backward: gate gradient + dense-layer gradients,
-    then the gradient wrt x).  Inside InvertedResidualChannelsFused the gate runs in the block's executor on the raw depthwise
-    output; this is the same arithmetic on an already activated tensor (identity BatchNorm coefficients, activation mode 0)."""
+    with the SE sequence of the fused block (_se_forward / _se_backward), which runs it on the raw depthwise output with the dw_bn
+    coefficients and the plan's packed weights; here on an already activated tensor: identity coefficients, weights packed on the spot."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, se_act, dtype):
@@ -466,28 +483,20 @@ class SEFunction(torch.autograd.Function):
         dev = x.device
         hid = w1.shape[0]
         HT = pads(C)
-        M, HW = N * H * W, H * W
+        M = N * H * W
         D = ops.zeros(M, HT, dtype=dtype, device=dev)
         D[:, :C] = x2d
         cmap = torch.full((HT,), -1, dtype=torch.int32, device=dev)
         cmap[:C] = torch.arange(C, dtype=torch.int32, device=dev)
-        w1m, w2m = w1.detach().reshape(hid, C).float(), w2.detach().reshape(C, hid).float()
-        w1p, w2t, b2p = (ops.zeros(hid, HT, dtype=torch.float32, device=dev), ops.zeros(hid, HT, dtype=torch.float32, device=dev),
-                         ops.zeros(HT, dtype=torch.float32, device=dev))
-        w1p[:, :C] = w1m
-        w2t[:, :C] = w2m.t()
+        w1p, w2t, b2p = (ops.zeros(*shape, dtype=torch.float32, device=dev) for shape in ((hid, HT), (hid, HT), (HT,)))
+        w1p[:, :C] = w1.detach().reshape(hid, C).float()
+        w2t[:, :C] = w2.detach().reshape(C, hid).float().t()
         b2p[:C] = b2.detach().float()
         one, zero = torch.ones(HT, dtype=torch.float32, device=dev), ops.zeros(HT, dtype=torch.float32, device=dev)
         one[C:] = 0
-        pooled, gate = _f32(N * HT, dev).view(N, HT), _f32(N * HT, dev).view(N, HT)
-        hpre = _f32(N * hid, dev).view(N, hid)
-        parts = ops.se_pool_parts(N, HW, HT)
-        pparts = _f32(parts * N * HT, dev).view(parts, N, HT)
-        ops.se_squeeze(D, one, zero, ACT_NONE, pparts, N, HW, HT)
-        ops.se_mlp_fwd(pparts, pooled, cmap, w1p, b1.detach().float().contiguous(), w2t, b2p, se_act, hpre, gate, N, HT, hid)
         S = torch.empty(M, HT, dtype=dtype, device=dev)
-        ops.se_scale(D, one, zero, ACT_NONE, gate, S, M, HW, HT)
-        ctx.save_for_backward(D, one, zero, gate, pooled, cmap, w1p, w2t, hpre)
+        sv = _se_forward(D, one, zero, ACT_NONE, S, cmap, w1p, b1.detach().float().contiguous(), w2t, b2p, se_act, hid, N, H * W, HT)
+        ctx.save_for_backward(D, one, zero, sv["gate"], sv["pooled"], cmap, w1p, w2t, sv["hpre"])
         ctx.dims = (N, H, W, C, HT, hid, se_act, dtype)
         return to_4d(S[:, :C], N, H, W, C)
 
@@ -496,20 +505,14 @@ class SEFunction(torch.autograd.Function):
         D, one, zero, gate, pooled, cmap, w1p, w2t, hpre = ctx.saved_tensors
         N, H, W, C, HT, hid, se_act, dtype = ctx.dims
         dev = D.device
-        M, HW = N * H * W, H * W
+        M = N * H * W
         g2d, _ = to_2d(gout, dtype)
         dS = ops.zeros(M, HT, dtype=dtype, device=dev)
         dS[:, :C] = g2d
-        dz2, dpooled = _f32(N * HT, dev).view(N, HT), _f32(N * HT, dev).view(N, HT)
-        parts = ops.se_pool_parts(N, HW, HT)
-        dgate = _f32(parts * N * HT, dev).view(parts, N, HT)
-        dz1 = _f32(N * hid, dev).view(N, hid)
         dw1, db1, dw2, db2 = (_f32(hid * C, dev, zero=True), _f32(hid, dev, zero=True), _f32(C * hid, dev, zero=True), _f32(C, dev, zero=True))
-        ops.se_bwd_gate(dS, D, one, zero, ACT_NONE, gate, pooled, cmap, w1p, w2t, hpre, dgate, dz2, dz1, dpooled, dw1, db1, dw2, db2, N, HW, HT, C,
-                        hid, se_act=se_act)
         g = torch.empty(M, HT, dtype=dtype, device=dev)
-        st = _stats(HT, dev)
-        ops.se_bwd_apply(dS, D, one, zero, ACT_NONE, gate, dpooled, g, st.t, M, HW, HT, stat_rows=st.rows)
+        _se_backward(dS, D, one, zero, ACT_NONE, dict(gate=gate, pooled=pooled, hpre=hpre), cmap, w1p, w2t, se_act, hid, dw1, db1, dw2, db2,
+                     C, g, _stats(HT, dev), N, H * W, HT)
         return (to_4d(g[:, :C], N, H, W, C), dw1.view(hid, C, 1, 1), db1, dw2.view(C, hid, 1, 1), db2, None, None)
 
 
@@ -548,16 +551,14 @@ def convbn_forward(pl, x, need_grad):
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
         M = N * Ho * Wo
         sv["kind"] = "dw"
-    bs = bn_uses_batch_stats(pl.bn)
     Cp = pad8(pl.cout)
     Y = torch.empty(M, Cp, dtype=T, device=dev) if sv["kind"] != "dw" else ops.zeros(M, Cp, dtype=T, device=dev)
-    st = _stats(pl.cout, dev, pl.bn["mgr"]) if bs else None
+    st = _stats(pl.cout, dev, pl.bn["mgr"]) if bn_uses_batch_stats(pl.bn) else None
     if sv["kind"] == "dw":
-        ops.dwconv_fwd(a2d, None, None, 0, pl.taps, Y, st.t if bs else None, pl.cout, N, H, W, pl.cout, pl.k, pl.stride,
-                       stat_rows=st.rows if bs else None)
+        ops.dwconv_fwd(a2d, None, None, 0, pl.taps, Y, stat_ld=pl.cout, N=N, H=H, W=W, C=pl.cout, k=pl.k, stride=pl.stride,
+                       **_fwd_stats(st, mode=False))
     else:
-        ops.gemm_nt(a2d, pl.W_pack, Y, M, pl.cout, K, stats=st.t if bs else None, stat_mode=STAT_SQ if bs else 0,
-                    stat_rows=st.rows if bs else None)
+        ops.gemm_nt(a2d, pl.W_pack, Y, M, pl.cout, K, **_fwd_stats(st))
     b = bn_forward_coeffs(pl.bn, st, M, dev)
     if act:
         _tap("convbn", pl, Y, b)
@@ -634,11 +635,9 @@ def tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, need_grad):
     a2d, (N, H, W, C) = to_2d(x, T)
     M = N * H * W
     act = lp.act
-    bs = bn_uses_batch_stats(lp.bn)
     L = torch.empty(M, lp.cout, dtype=T, device=dev)
-    st = _stats(lp.cout, dev, lp.bn["mgr"]) if bs else None
-    ops.gemm_nt(a2d, lp.W_pack, L, M, lp.cout, lp.cin, stats=st.t if bs else None, stat_mode=STAT_SQ if bs else 0,
-                stat_rows=st.rows if bs else None)
+    st = _stats(lp.cout, dev, lp.bn["mgr"]) if bn_uses_batch_stats(lp.bn) else None
+    ops.gemm_nt(a2d, lp.W_pack, L, M, lp.cout, lp.cin, **_fwd_stats(st))
     b = bn_forward_coeffs(lp.bn, st, M, dev)
     if act:
         _tap("convbn", lp, L, b)

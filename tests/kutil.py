@@ -107,7 +107,7 @@ def bf16_storage():
     lib = _lib.load()
 
     def pred(k, stride, N, C, H, W, slab):
-        if not slab or os.environ.get("ATOMNAS_PLAIN_HIDDEN", "0") != "0":
+        if not slab:
             return False, False
         return (bool(lib.atomnas_dwconv_mm_supported(N, H, W, C, k, stride, 1, 0)), bool(lib.atomnas_dwconv_mm_supported(N, H, W, C, k, stride, 1, 1)))
     return orc.bf16_storage_mm(pred)
