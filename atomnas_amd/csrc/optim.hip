@@ -122,6 +122,35 @@ __global__ __launch_bounds__(256) void k_scale_by(float* __restrict__ x, long n,
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= f;
 }
 
+// Fold of one micro-batch into a running sum (gradient accumulation, engine.TrainStep with accum_steps > 1):
+//   acc = (first ? 0 : acc) + cur;   then   cur = acc * inv_count (last)   or   cur = base (not last; base null: cur stays)
+// One thread owns an element from the read to both writes, 16-byte pieces plus a ragged tail of up to 3 floats: no atomics, no order
+// between threads to depend on.  The BN running statistics use it with base = their values at the start of the step (every
+// micro-batch updates from the same start, the step leaves the mean); the gradient arena with base = null and inv_count = 1.
+__global__ __launch_bounds__(256) void k_accum_fold(float* __restrict__ acc, float* __restrict__ cur, const float* __restrict__ base,
+                                                    long n, int first, int last, float inv_count) {
+#pragma clang fp contract(off)
+  const long n4 = n >> 2;
+  f32x4* __restrict__ a4 = reinterpret_cast<f32x4*>(acc);
+  f32x4* __restrict__ c4 = reinterpret_cast<f32x4*>(cur);
+  const f32x4* __restrict__ b4 = reinterpret_cast<const f32x4*>(base);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    f32x4 a = first ? f32x4{0.f, 0.f, 0.f, 0.f} : a4[i];
+    a = a + c4[i];
+    a4[i] = a;
+    if (last) c4[i] = a * inv_count;
+    else if (base) c4[i] = b4[i];
+  }
+  const long t = n4 * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
+    float a = first ? 0.f : acc[t];
+    a = a + cur[t];
+    acc[t] = a;
+    if (last) cur[t] = a * inv_count;
+    else if (base) cur[t] = base[t];
+  }
+}
+
 // zero-fill with 16-byte stores (n16 pieces) plus a 4-byte tail.  A kernel rather than hipMemsetAsync: as a captured memset node
 // the 44 MB gradient arena was not cleared on replay (bs 256 supernet, ROCm 7.2: the replayed step trained on accumulated
 // gradients), while kernel nodes replay faithfully.
@@ -215,6 +244,19 @@ extern "C" int atomnas_scale_by(float* x, long n, const float* hyper, int idx, v
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(k_scale_by, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, hyper, idx);
   return check_launch("scale_by");
+}
+
+// acc = (first ? 0 : acc) + cur over n floats, then cur = acc * inv_count (last) or cur = base (not last; base may be null: cur is left
+// as it is).  acc, cur and base are 16-byte aligned and do not overlap.  One launch, capturable.
+extern "C" int atomnas_accum_fold(float* acc, float* cur, const float* base, long n, int first, int last, float inv_count, void* stream) {
+  ATOMNAS_REQUIRE(acc && cur && n > 0, "accum_fold: bad arguments");
+  ATOMNAS_REQUIRE((((unsigned long long)acc | (unsigned long long)cur | (unsigned long long)base) & 15ull) == 0,
+                  "accum_fold: needs 16-byte aligned pointers");
+  long blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_accum_fold, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, cur, base, n, first, last, inv_count);
+  return check_launch("accum_fold");
 }
 
 // p[0 .. bytes) = 0 (gradient arena, per-step scalars, accumulated outputs); p 16-byte aligned, bytes a multiple of 4

@@ -12,6 +12,13 @@ backward, bucket by bucket on a side stream as soon as the blocks that own a buc
 module order, backward runs it from the end), and is captured into the same hipGraph as the kernels ("graph" mode); the 1/world
 scale rides in the optimizer kernel.  Other backends (gloo in the tests) and a failed capture use one blocking all-reduce between
 two graphs ("host" mode).
+
+Gradient accumulation (accum_steps = A > 1): one optimizer step consumes A static batches, each a "virtual rank" of a W * A rank
+data-parallel job with allreduce_bn.  accumulate() runs forward + backward of a micro-batch, step() the last one plus everything
+that happens once per optimizer step.  Every micro-batch writes its gradients into the zeroed arena G exactly as a step of its own
+would; one fold launch adds G to a second arena in micro-batch order, and the last fold leaves the sum in G (a second arena because
+some gradients receive two additions per backward).  The BatchNorm running statistics of every micro-batch start
+from the values at the start of the step, and the step leaves their mean.  A = 1 issues exactly what it did without the feature.
 """
 import os
 
@@ -31,7 +38,7 @@ HYP_SUMMED_RANKS = 4   # engine-owned slot of the per-step scalar vector (runtim
 class TrainStep:
 
     def __init__(self, model, optimizer, ema=None, prune_info=None, weight_decay=1e-5, wd_method='mnas', label_smoothing=0.1,
-                 batch_size=256, image_size=224, use_graph=True, process_group=None, world_size=1, allreduce_bn=False):
+                 batch_size=256, image_size=224, use_graph=True, process_group=None, world_size=1, allreduce_bn=False, accum_steps=1):
         self.model, self.optimizer, self.ema, self.prune_info = model, optimizer, ema, prune_info
         self.weight_decay, self.wd_method = weight_decay, wd_method
         self.use_graph = use_graph
@@ -65,6 +72,17 @@ class TrainStep:
         self.global_step = 0
         self._seed_grad = None
         self._agree = torch.ones(1, dtype=torch.float32, device=dev)   # capture outcome, MIN-reduced over the ranks
+        # gradient accumulation: accum_steps micro-batches per optimizer step (1: nothing below is ever allocated, captured or launched)
+        if isinstance(accum_steps, bool) or int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise ValueError("accum_steps must be a positive integer, got %r" % (accum_steps,))
+        self.accum_steps = int(accum_steps)
+        self._pending = 0              # micro-batches accumulated since the last step() / reset_accumulation()
+        self._group_version = -1       # arena version the current group started on
+        self._acc_version = -1
+        self._acc = self._sacc = self._sbase = None   # running sums of G (+ the CE mean behind it) and S, S at the start of the step
+        self.g_mb = self.g_last = self.g_all_last = None   # graphs of a micro-batch / the last one / the last one with its collectives
+        self._pool = None              # private pool shared by the graphs above: they never run concurrently
+        self._fold_buckets = False     # the bucket hook folds its slice of G before the collective (last micro-batch, "graph" mode)
 
     # ---- pieces
     def _prune_weights(self):
@@ -120,6 +138,8 @@ class TrainStep:
             _, lo, hi = self._buckets[self._fired]
             self._fired += 1
             ops.reduce_flush()   # the bucket's weight gradients are complete only after their recorded reductions
+            if self._fold_buckets:   # last micro-batch of an accumulated step: the collective travels the SUM of the micro-batches
+                ops.accum_fold(self._acc[lo:hi], self.mgr.G[lo:hi], None, hi - lo, False, True)
             cur = torch.cuda.current_stream()
             self._comm.wait_stream(cur)
             with torch.cuda.stream(self._comm):
@@ -131,18 +151,26 @@ class TrainStep:
         dist.all_reduce(mgr.S, group=self.pg)
         ops.scale_by(mgr.S, mgr.nS, mgr.hyper, ops.HYP_GRAD_SCALE)
 
-    def _fwd_bwd_overlapped(self):
+    def _fwd_bwd_overlapped(self, last=None):
+        """last=True: the last micro-batch of an accumulated step (every bucket is folded into the running sum before its collective,
+        the statistics are folded before theirs); None: the plain step"""
         mgr = self.mgr
         self._fired = 0
         mgr.grad_done_cb = self._on_grad_done
+        self._fold_buckets = last is not None
         try:
-            self._fwd_bwd()
+            self._fwd_bwd(last)
         finally:
             mgr.grad_done_cb = None
+            self._fold_buckets = False
         cur = torch.cuda.current_stream()
+        if last is not None:
+            self._fold_stats(False, True, True)
         while self._fired < len(self._buckets):   # plans that took no part in this backward (none in the networks of this path)
             _, lo, hi = self._buckets[self._fired]
             self._fired += 1
+            if last is not None:
+                ops.accum_fold(self._acc[lo:hi], mgr.G[lo:hi], None, hi - lo, False, True)
             self._comm.wait_stream(cur)
             with torch.cuda.stream(self._comm):
                 dist.all_reduce(mgr.G[lo:hi], group=self.pg)
@@ -152,15 +180,30 @@ class TrainStep:
                 self._reduce_bn()
         cur.wait_stream(self._comm)
 
-    def _fwd_bwd(self):
+    def _fold_stats(self, first, last, reducing):
+        """The BatchNorm running statistics of one micro-batch into their running sum: S goes back to its values at the start of the
+        step, or (last) becomes the mean over the micro-batches.  Where _reduce_bn follows it leaves the plain sum: that collective
+        multiplies by 1 / (ranks * micro-batches) itself (HYP_GRAD_SCALE), one multiply as over that many real ranks."""
+        mgr = self.mgr
+        inv = 1.0 if (reducing and self.allreduce_bn) else 1.0 / self.accum_steps
+        ops.accum_fold(self._sacc, mgr.S, self._sbase, mgr.nS, first, last, inv)
+
+    def _fwd_bwd(self, last=None):
         """zero_grad -> forward -> label-smoothed CE (mean) -> backward, HIP launches only.  The regularisers do not go through
         autograd here: their gradients are added in _opt (L1: one launch on the gamma job table after the all-reduce; L2: inside
         the optimizer kernel), which is the same arithmetic as the reference's `loss + l2 + l1` backward because both terms are
         identical on every rank (train.py:171-185)."""
         mgr = self.mgr
         mgr.zero_grad()
-        ops.zero_(self._scal)
-        loss = self.model(self.x, loss_args=(self.y, self.label_smoothing, self.loss_vec, self.topk, self.loss[0:1]))
+        # last False / True: a micro-batch of an accumulated step.  Its scalars were cleared when the group started (the hit counts add
+        # up over the micro-batches), and the BatchNorm counters advance with the last micro-batch only
+        if last is None:
+            ops.zero_(self._scal)
+        mgr.hold_counters = last is False
+        try:
+            loss = self.model(self.x, loss_args=(self.y, self.label_smoothing, self.loss_vec, self.topk, self.loss[0:1]))
+        finally:
+            mgr.hold_counters = False
         if self._seed_grad is None or self._seed_grad.shape != loss.shape:
             self._seed_grad = torch.ones_like(loss)   # allocated once: backward() would fill a fresh ones tensor every step
         # the fixed-order sums of the weight-gradient partials are recorded during backward and run as a few batched launches
@@ -170,6 +213,14 @@ class TrainStep:
             loss.backward(self._seed_grad)
         finally:
             ops.reduce_defer(False)   # flushes on the current stream
+        if last is not None:
+            nP = mgr.nP
+            if not self._fold_buckets:   # G -> running sum; after the last micro-batch G holds the sum in micro-batch order
+                ops.accum_fold(self._acc, mgr.G, None, nP, False, last)
+            # CE mean -> running sum behind the gradients'; after the last micro-batch loss[0] is the mean of the micro-batch means
+            ops.accum_fold(self._acc[nP:], self.loss, None, 1, False, last, 1.0 / self.accum_steps)
+            if not last:
+                ops.add_i64(mgr.step_counter, 1)   # every micro-batch draws its own dropout masks (the last one's advance is in _opt)
 
     def _opt(self):
         """[gradients summed over ranks] -> + world * rho * penalty * sign(gamma) -> the optimizer's fused launch (RMSprop or SGD) on
@@ -185,8 +236,10 @@ class TrainStep:
             ops.ema_update(mgr.SEMA, mgr.S, mgr.nS, mgr.hyper)
         ops.add_i64(mgr.step_counter, 1)
 
-    def _capture(self, want_overlapped=False):
-        """Captures what is missing: the one-graph form with the in-graph collectives (want_overlapped, comm mode "graph") and / or
+    def _capture(self, want_overlapped=False, accum=False):
+        """accum: the graphs of an accumulated step instead (a micro-batch, the last micro-batch, the last one with its in-graph
+        collectives; they share one private pool, as no two of them ever run at the same time) -- the optimizer graph is the same.
+        Captures what is missing: the one-graph form with the in-graph collectives (want_overlapped, comm mode "graph") and / or
         the forward-backward + optimizer pair that runs without a collective or around a blocking one.  Graphs that exist are kept:
         a step(reduce=False) between reducing steps must not drop the overlapped graph."""
         mgr = self.mgr
@@ -195,6 +248,7 @@ class TrainStep:
         # warm-up outside capture (allocator pools, lazy initialisation); it must not leave a trace in the training state:
         # BN running statistics / counters are snapshotted and restored, gradients are re-zeroed by the step itself
         keep_s, keep_c = mgr.S.clone(), mgr.CNT.clone()
+        keep_scal = self._scal.clone() if accum else None   # a group may be under way: its hit counts live there
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -204,9 +258,15 @@ class TrainStep:
         torch.cuda.synchronize()
         mgr.S.copy_(keep_s)
         mgr.CNT.copy_(keep_c)
+        if accum:
+            self._scal.copy_(keep_scal)
+            if self._pool is None:
+                self._pool = torch.cuda.graph_pool_handle()
+        g_over = "g_all_last" if accum else "g_all"
+        pool = dict(pool=self._pool) if accum else {}
         # thread_local: the RCCL watchdog thread of a process group polls events while we capture; in the default "global" mode
         # such a call from another thread invalidates the capture
-        if want_overlapped and self.comm_mode == "graph" and self.g_all is None:
+        if want_overlapped and self.comm_mode == "graph" and getattr(self, g_over) is None:
             # one graph: kernels, bucketed RCCL all-reduces on the side stream, optimizer tail
             ok = True
             try:
@@ -217,10 +277,10 @@ class TrainStep:
                 torch.cuda.current_stream().wait_stream(self._comm)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._fwd_bwd_overlapped()
+                with torch.cuda.graph(g, capture_error_mode="thread_local", **pool):
+                    self._fwd_bwd_overlapped(True if accum else None)
                     self._opt()
-                self.g_all = g
+                setattr(self, g_over, g)
             except Exception as e:   # a runtime that cannot capture the collective: fall back to the blocking form
                 import logging
                 logging.warning("capturing the gradient all-reduce failed (%s); using one blocking all-reduce between two graphs", e)
@@ -232,8 +292,21 @@ class TrainStep:
             dist.all_reduce(self._agree, op=dist.ReduceOp.MIN, group=self.pg)
             if float(self._agree.item()) < 0.5:
                 self.comm_mode = "host"
-                self.g_all = None
-        if self.g_fwd_bwd is None and not (want_overlapped and self.g_all is not None):
+                self.g_all = self.g_all_last = None
+        if accum:
+            if self.g_mb is None:
+                self.g_mb = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_mb, capture_error_mode="thread_local", **pool):
+                    self._fwd_bwd(False)
+            if self.g_last is None and not (want_overlapped and self.g_all_last is not None):
+                self.g_last = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_last, capture_error_mode="thread_local", **pool):
+                    self._fwd_bwd(True)
+                if self.g_opt is None:
+                    self.g_opt = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local", **pool):
+                        self._opt()
+        elif self.g_fwd_bwd is None and not (want_overlapped and self.g_all is not None):
             self.g_fwd_bwd = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_fwd_bwd, capture_error_mode="thread_local"):
                 self._fwd_bwd()
@@ -251,16 +324,105 @@ class TrainStep:
         # the collective can be forced on a single rank to exercise RCCL next to graph replay on a one-GPU box
         return self.world_size > 1 or (bool(os.environ.get("ATOMNAS_FORCE_ALLREDUCE")) and dist.is_initialized())
 
+    def _sync_arenas(self):
+        """follows an arena rebuild (a shrink): graphs and buckets of the old arenas are dropped"""
+        mgr = self.mgr
+        if mgr.dirty or self._version != mgr.version:
+            mgr.ensure()
+            self.g_fwd_bwd = self.g_opt = self.g_all = None
+            self.g_mb = self.g_last = self.g_all_last = None
+            self._buckets = []
+
+    # ---- gradient accumulation
+    @property
+    def pending(self):
+        """micro-batches accumulated since the last step() / reset_accumulation()"""
+        return self._pending
+
+    def _check_group(self):
+        if self._pending and (self.mgr.dirty or self.mgr.version != self._group_version):
+            raise RuntimeError("the arenas were rebuilt (a shrink?) inside a group of accumulated micro-batches: the running sums belong "
+                               "to the old layout.  Shrink between optimizer steps, or call reset_accumulation() and start the group again")
+
+    def reset_accumulation(self):
+        """discards a partial group: the next accumulate() starts from zero.  The running statistics are already back at their values
+        of the start of the step (every fold leaves them there); the dropout counter steps back to where the group began."""
+        if self._pending and not self.mgr.dirty and self.mgr.version == self._group_version:
+            ops.add_i64(self.mgr.step_counter, -self._pending)
+        self._pending = 0
+
+    def accumulate(self):
+        """Forward and backward of the current static batch into the running sums of an accumulated step (accum_steps > 1); the
+        first call after a step() or reset_accumulation() starts them from zero.  The last micro-batch of a group belongs to step()."""
+        mgr = self.mgr
+        A = self.accum_steps
+        if self._pending >= A - 1:
+            raise RuntimeError("accumulate() with %d of %d micro-batches pending: the last micro-batch of a group belongs to step()"
+                               % (self._pending, A))
+        self._check_group()
+        if self._pending == 0:
+            self._sync_arenas()
+            if self._acc_version != mgr.version:   # the sums follow the arenas' layout
+                f32 = dict(dtype=torch.float32, device=mgr.P.device)
+                self._acc = torch.empty(mgr.nP + runtime.ALIGN, **f32)
+                self._sacc, self._sbase = torch.empty(mgr.nS, **f32), torch.empty(mgr.nS, **f32)
+                self._acc_version = mgr.version
+            self._group_version = mgr.version
+            # outside the graphs: two memsets and the snapshot of the statistics every micro-batch of this step starts from
+            self._acc.zero_()
+            self._scal.zero_()
+            self._sbase.copy_(mgr.S)
+        if self.use_graph:
+            if self.g_mb is None:
+                self._tables()
+                self._capture(accum=True)
+            self.g_mb.replay()
+        else:
+            self._fwd_bwd(False)
+        self._fold_stats(self._pending == 0, False, False)
+        self._pending += 1
+
+    def _last_micro_batch(self, do_reduce, overlapped):
+        """step() of an accumulated group: the last micro-batch, the collective over the real ranks, the optimizer tail"""
+        mgr = self.mgr
+        if self.use_graph:
+            if overlapped and self.g_all_last is None:
+                self._capture(want_overlapped=True, accum=True)   # may agree on "host" over the ranks
+                overlapped = do_reduce and self.comm_mode == "graph"
+            if overlapped and self.g_all_last is not None:
+                self.g_all_last.replay()
+                return
+            if self.g_last is None or self.g_opt is None:
+                self._capture(accum=True)
+            self.g_last.replay()
+        elif overlapped:
+            self._fwd_bwd_overlapped(True)
+            self._opt()
+            return
+        else:
+            self._fwd_bwd(True)
+        self._fold_stats(False, True, do_reduce)
+        if do_reduce:
+            dist.all_reduce(mgr.G, group=self.pg)
+            if self.allreduce_bn:
+                self._reduce_bn()
+        if self.use_graph:
+            self.g_opt.replay()
+        else:
+            self._opt()
+
     def step(self, lr=None, rho=0.0, ema_decay=None, reduce=None):
         """One iteration on the current static batch.  lr defaults to the optimizer's group lr.  reduce: None = all-reduce the
         gradient arena when world_size > 1; False = never (bench.py's single-rank profiling pass: the other ranks wait at a
         barrier, so no collective may be issued)."""
         mgr = self.mgr
+        A = self.accum_steps
+        if self._pending != A - 1:
+            raise RuntimeError("step() runs the last of %d micro-batches: %d accumulate() calls must come first, %d were made"
+                               % (A, A - 1, self._pending))
+        self._check_group()
         do_reduce = self._wants_reduce() if reduce is None else bool(reduce)
-        if mgr.dirty or self._version != mgr.version:
-            mgr.ensure()
-            self.g_fwd_bwd = self.g_opt = self.g_all = None
-            self._buckets = []
+        self._sync_arenas()
         if do_reduce and self.comm_mode is None:
             backend = dist.get_backend(self.pg) if dist.is_initialized() else None
             # ATOMNAS_OVERLAP_ALLREDUCE: "0" never, "force" with any backend (tests drive the bucketed path eagerly with gloo ranks)
@@ -276,7 +438,7 @@ class TrainStep:
         h[ops.HYP_RHO] = float(rho)
         # the scales follow what THIS step does: a step without the collective (bench.py's single-rank profile pass) trains on its own
         # gradients, not on gradients shrunk by 1 / world
-        eff_world = float(max(self.world_size, 1)) if do_reduce else 1.0
+        eff_world = (float(max(self.world_size, 1)) if do_reduce else 1.0) * A   # micro-batches count as ranks
         h[ops.HYP_GRAD_SCALE] = 1.0 / eff_world
         h[HYP_SUMMED_RANKS] = eff_world
         if self.ema is not None:
@@ -285,7 +447,9 @@ class TrainStep:
             h[ops.HYP_EMA_DECAY] = -1.0
         mgr.push_hyper()
         overlapped = do_reduce and self.comm_mode == "graph"
-        if self.use_graph:
+        if A > 1:
+            self._last_micro_batch(do_reduce, overlapped)
+        elif self.use_graph:
             if overlapped and self.g_all is None:
                 self._capture(want_overlapped=True)   # may agree on "host" over the ranks
                 overlapped = do_reduce and self.comm_mode == "graph"
@@ -314,6 +478,7 @@ class TrainStep:
         # scales behind (host copy only: the device vector is re-staged by whoever launches next)
         h[ops.HYP_GRAD_SCALE] = 1.0
         h[HYP_SUMMED_RANKS] = 1.0
+        self._pending = 0
         self.global_step += 1
         if self.ema is not None:   # bookkeeping the reference keeps per variable (utils/optim.py:62-63); checkpointed
             self.ema.note_updates(1, float(h[ops.HYP_EMA_DECAY]))

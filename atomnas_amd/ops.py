@@ -516,6 +516,11 @@ def scale_by(x, n, hyper, idx):
     call("atomnas_scale_by", _p(x), n, _p(hyper), idx, _stream())
 
 
+def accum_fold(acc, cur, base, n, first, last, inv_count=1.0):
+    """acc = (0 if first else acc) + cur over n floats; then cur = acc * inv_count (last) or cur = base (not last; base None: cur stays)"""
+    call("atomnas_accum_fold", _p(acc), _p(cur), _p(base), int(n), int(bool(first)), int(bool(last)), float(inv_count), _stream())
+
+
 def pack_weights(arena, packbuf, jobs_dev, njobs, dtype):
     call("atomnas_pack_weights", _p(arena), _p(packbuf), _p(jobs_dev), njobs, dt_code(dtype), _stream())
 

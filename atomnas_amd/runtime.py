@@ -766,10 +766,15 @@ class ArenaManager:
             self._reset_stats()
         self._depth += 1
 
+    # engine.TrainStep sets it around the forward of every micro-batch of an accumulated step but the last: num_batches_tracked
+    # advances once per optimizer step, and every micro-batch of a step sees the same counters (cumulative-average BatchNorms)
+    hold_counters = False
+
     def leave(self):
         self._depth -= 1
         if self._depth == 0 and self.bn_trained:
-            ops.add_i64(self.CNT, 1)
+            if not self.hold_counters:
+                ops.add_i64(self.CNT, 1)
             self.bn_trained = False
 
 

@@ -147,14 +147,23 @@ def profiling(model, use_cuda=True):
     model_profiling(model, FLAGS.image_size, FLAGS.image_size, verbose=False)
 
 
+def grad_accum_steps():
+    """the yaml's grad_accum_steps (default 1) as a positive int; anything else is a ValueError"""
+    a = FLAGS.get('grad_accum_steps', 1)
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or int(a) != a or int(a) < 1:
+        raise ValueError('grad_accum_steps must be a positive integer, got {!r}'.format(a))
+    return int(a)
+
+
 def setup_distributed(num_images=None):
-    """batch_size = world * per_gpu_batch_size; lr = base_lr * batch / base_total_batch; steps per epoch = ceil(N / batch)
-    (common.py:185-209)."""
+    """batch_size = world * per_gpu_batch_size * grad_accum_steps; lr = base_lr * batch / base_total_batch; steps per epoch =
+    ceil(N / batch) (common.py:185-209; the micro-batches of an accumulated step count as further ranks: engine.TrainStep)."""
+    accum = grad_accum_steps()
     if FLAGS.use_distributed:
         udist.init_dist()
-        FLAGS.batch_size = udist.get_world_size() * FLAGS.per_gpu_batch_size
+        FLAGS.batch_size = udist.get_world_size() * FLAGS.per_gpu_batch_size * accum
     else:
-        FLAGS.batch_size = FLAGS.per_gpu_batch_size
+        FLAGS.batch_size = FLAGS.per_gpu_batch_size * accum
     FLAGS._loader_batch_size = FLAGS.per_gpu_batch_size
     if 'base_lr' in FLAGS:
         FLAGS.lr = FLAGS.base_lr * (FLAGS.batch_size / FLAGS.base_total_batch)

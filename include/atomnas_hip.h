@@ -261,6 +261,10 @@ int atomnas_ema_update(float* shadow, const float* x, long n, const float* hyper
 /* x[i] *= hyper[idx]: the BN running statistics summed over the ranks become their average (utils/distributed.py:164-169,
  * allreduce_bn; hyper[3] = 1 / world) */
 int atomnas_scale_by(float* x, long n, const float* hyper, int idx, void* stream);
+/* fold of one micro-batch into a running sum (gradient accumulation): acc = (first ? 0 : acc) + cur over n floats, then
+ * cur = acc * inv_count (last) or cur = base (not last; base NULL: cur is left as it is).  16-byte aligned, non-overlapping
+ * pointers; one capturable launch without atomics.  Added within ABI 9 (a new symbol, nothing existing changes). */
+int atomnas_accum_fold(float* acc, float* cur, const float* base, long n, int first, int last, float inv_count, void* stream);
 /* housekeeping of the step without framework kernels: zero-fill (16-byte aligned, whole words), int64 counters += v
  * (num_batches_tracked of the BatchNorms, the dropout step counter) */
 int atomnas_zero(void* p, long bytes, void* stream);

@@ -265,7 +265,8 @@ def train_val_test():
                             wd_method=FLAGS.weight_decay_method, label_smoothing=FLAGS.label_smoothing,
                             batch_size=FLAGS.per_gpu_batch_size, image_size=FLAGS.image_size,
                             world_size=udist.get_world_size_fallback(),
-                            allreduce_bn=bool(FLAGS.use_distributed and FLAGS.get('allreduce_bn', False)))
+                            allreduce_bn=bool(FLAGS.use_distributed and FLAGS.get('allreduce_bn', False)), accum_steps=mc.grad_accum_steps())
+    accum = step.accum_steps   # loader batches per optimizer step; _steps_per_epoch / max_steps_per_epoch count optimizer steps
     val_criterion = optim.CrossEntropyLabelSmooth(FLAGS.model_kwparams['num_classes'], 0.0, reduction='none')
     val_meters = mc.get_meters('val')
     steps_per_epoch = FLAGS.get('max_steps_per_epoch', None) or FLAGS._steps_per_epoch
@@ -273,18 +274,22 @@ def train_val_test():
     for epoch in range(last_epoch + 1, FLAGS.num_epochs):
         model.train()
         t0, seen = time.time(), 0
-        batches = (device_batches(LOADERS[0], steps_per_epoch) if LOADERS is not None else
-                   fake_batches(FLAGS.per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'], steps_per_epoch,
+        batches = (device_batches(LOADERS[0], steps_per_epoch * accum) if LOADERS is not None else
+                   fake_batches(FLAGS.per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'], steps_per_epoch * accum,
                                 FLAGS.get('random_seed', 0) + rank + 1000 * epoch))
+        step.reset_accumulation()   # a trailing partial group of the last epoch is dropped, as a short last batch is
         for x, y in batches:
             if x.shape[0] != FLAGS.per_gpu_batch_size:
                 continue   # a short last batch: the captured step has a static batch (drop_last: True avoids drawing it)
             step.set_batch(x, y)
+            seen += x.shape[0]
+            if step.pending < accum - 1:
+                step.accumulate()
+                continue
             step.global_step = FLAGS._global_step
             step.step(lr=optimizer.param_groups[0]['lr'], rho=rho_scheduler(FLAGS._global_step))
             lr_scheduler.step()   # (allreduce_bn, when configured, happens inside the step: before the EMA, as in the reference)
             FLAGS._global_step += 1
-            seen += x.shape[0]
             if FLAGS._global_step % FLAGS.log_interval == 0 and udist.is_master():
                 ce, l2, l1 = step.loss.tolist()   # the only host synchronisation of the interval
                 dt = time.time() - t0
