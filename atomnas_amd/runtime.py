@@ -15,6 +15,12 @@ projection weights one [oup, HT] matrix, BN vectors one [HT] vector, where each 
 rounded up to 16 channels, one slab of the slab-major hidden tensors (HT = sum of padded segments).  Padding entries are zeros that belong to no Parameter; they
 stay zero under training (their gradients are identically zero) and let every kernel use aligned 16-byte accesses after a
 shrink has produced ragged channel counts (13, 139, ...).
+
+Where everything lives is decided by ONE walk of the module tree, arena_layout(model, compute_dtype) -> ArenaLayout: offsets in the
+arenas and pack buffers, the bind list, the pack and fold jobs and one description per plan.  It is integer arithmetic on module
+attributes, runs on a CPU model and is pinned by tests/golden/arena_layout.json (tools/make_arena_layout.py): a new slot or table is
+added in the walker that owns the module kind, and the table shows what moved.  ArenaManager.materialize is then four steps: layout,
+allocate, migrate the values (one job-table launch), bind the plans' views.
 """
 import collections
 import ctypes
@@ -54,10 +60,39 @@ class _Layout:
     def __init__(self):
         self.size = 0
 
-    def take(self, numel):
+    def take(self, numel, align=ALIGN):
         off = self.size
-        self.size = _align(off + max(int(numel), 1))
+        self.size = _align(off + max(int(numel), 1), align)
         return off
+
+
+class _PackJob(ctypes.Structure):   # atomnas_pack_weights / atomnas_gather_jobs
+    _fields_ = [("src_off", ctypes.c_long), ("dst_off", ctypes.c_long), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
+                ("src_ld", ctypes.c_int), ("dst_ld", ctypes.c_int), ("c_off", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+class _FoldJob(ctypes.Structure):   # ops.fold_jobs, csrc/reduce.hip k_fold_jobs
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_ld", ctypes.c_long), ("dst_ld", ctypes.c_long),
+                ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("blk0", ctypes.c_uint), ("pad_", ctypes.c_int)]
+
+
+class _RegJob(ctypes.Structure):    # atomnas_reg_value / atomnas_reg_grad
+    _fields_ = [("off", ctypes.c_long), ("count", ctypes.c_int), ("coef", ctypes.c_float)]
+
+
+def _device_table(struct, rows, dev):
+    """the rows as an array of `struct` in device memory (a byte tensor)"""
+    arr = (struct * len(rows))(*[struct(*r) for r in rows])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(dev)
+
+
+def _view(arena, off, shape, strides):
+    if strides is None:
+        n = 1
+        for s in shape:
+            n *= s
+        return arena[off:off + n].view(shape)
+    return torch.as_strided(arena, shape, strides, off)
 
 
 class PwPack:
@@ -78,6 +113,242 @@ class BlockPlan:
 class SimplePlan:
     def __deepcopy__(self, memo):
         return None
+
+
+class ArenaLayout:
+    """Where everything of one model lives, as plain data (arena_layout): integer arithmetic on module attributes.  The walkers below are
+    the one place that hands out a slot; ArenaManager.materialize allocates, migrates and binds what they wrote down."""
+
+    def __init__(self, compute_dtype):
+        self.compute_dtype = compute_dtype
+        self.lp, self.ls, self.lc = _Layout(), _Layout(), _Layout()      # params / bn stats / counters
+        self.lpk, self.lpf, self.lfw = _Layout(), _Layout(), _Layout()   # packed weights (T) / packed depthwise taps (fp32) / fold scratch
+        self.binds = []        # (arena name, module, attribute, offset, shape, strides) of every parameter and buffer, in migration order
+        self.reg_slots = []    # (kind, offset, numel) of weight slots for the L2 regulariser: dense / dw / fc / fcbias
+        self.jobsT, self.jobsF = [], []   # pack jobs into packT / packF: the rows of _PackJob
+        self.fold_jobs = []    # fold jobs of the fused blocks: (scratch offset, gradient-arena offset, src_ld, dst_ld, rows, cols)
+        self.plans = []        # (module, plan carrying its scalar fields, dict(so=slot offsets, pk=pack offsets, mods=BatchNorms, act=module))
+
+    @property
+    def sizes(self):
+        """elements of P (= G, SQ, BUF, EMA), S (= SEMA), CNT, packT, packF and the fold scratch FW"""
+        return dict(P=max(self.lp.size, ALIGN), S=max(self.ls.size, ALIGN), CNT=max(self.lc.size, 8), packT=max(self.lpk.size, ALIGN),
+                    packF=max(self.lpf.size, ALIGN), FW=max(self.lfw.size, ALIGN))
+
+    # ---- slots
+    def param(self, mod, attr, off, shape, strides=None):
+        self.binds.append(("P", mod, attr, off, tuple(shape), strides))
+
+    def weight(self, kind, numel):
+        """a parameter slot that the L2 regulariser covers whole"""
+        off = self.lp.take(numel)
+        self.reg_slots.append((kind, off, numel))
+        return off
+
+    def bn_slots(self, C):
+        return dict(g=self.lp.take(C), b=self.lp.take(C), rm=self.ls.take(C), rv=self.ls.take(C))
+
+    def bind_bn(self, bn, slots, seg, c):
+        if bn.affine:
+            self.param(bn, "weight", slots["g"] + seg, (c,))
+            self.param(bn, "bias", slots["b"] + seg, (c,))
+        if bn.track_running_stats:
+            self.binds.append(("S", bn, "running_mean", slots["rm"] + seg, (c,), None))
+            self.binds.append(("S", bn, "running_var", slots["rv"] + seg, (c,), None))
+            self.binds.append(("CNT", bn, "num_batches_tracked", self.lc.take(1, 1), (), None))
+
+    def pw_pack(self, rows, cols, pieces):
+        """T pack buffers of W[rows][cols] and of its transpose, filled from `pieces` of the master: (src_off, rows, cols, src_ld, first
+        row, first column) each.  Returns (offset, padded rows, ld) of both."""
+        ldw, ldt = pad32(cols), pad32(rows)
+        o_w, o_t = self.lpk.take(pad64(rows) * ldw), self.lpk.take(pad64(cols) * ldt)
+        for src, r, c, src_ld, row0, col0 in pieces:
+            self.jobsT.append((src, o_w + row0 * ldw, r, c, src_ld, ldw, col0, 0))
+            self.jobsT.append((src, o_t + row0, r, c, src_ld, ldt, col0, 1))
+        return (o_w, pad64(rows), ldw), (o_t, pad64(cols), ldt)
+
+    def dw_taps(self, src_off, c, kk):
+        """fp32 tap-major [kk][c] copy of a depthwise weight [c][kk]"""
+        o_f = self.lpf.take(kk * c)
+        self.jobsF.append((src_off, o_f, c, kk, kk, c, 0, 2))
+        return (o_f, kk, c)
+
+    def _done(self, m, pl, **info):
+        pl.g_hi = self.lp.size
+        self.plans.append((m, pl, info))
+
+    # ---- walkers
+    def block(self, name, m):
+        """InvertedResidualChannels and InvertedResidualChannelsFused (models/mobilenet_base.py).  The kernels run both on the same
+        padded-segment layout: every branch owns a segment of the hidden tensors, padded to whole slabs (HT = sum of the segments).  Two
+        things differ.  The branch block's masters ARE that layout (one padded [HT] matrix / vector that the branches' parameters are
+        views of); the fused block has ONE expand conv / BN and ONE projection conv over all `total` hidden channels, CONTIGUOUS masters
+        as the reference's state_dict has them, which reach the padded layout through per-segment pack jobs and leave it through
+        per-segment fold jobs.  And only the fused block carries SE."""
+        from .models import mobilenet_base as mb  # local import: avoids a cycle
+        fused = isinstance(m, mb.InvertedResidualChannelsFused)
+        pl = BlockPlan()
+        pl.g_lo = self.lp.size
+        pl.name, pl.module, pl.fused = name, m, fused
+        inp, oup = pl.inp, pl.oup = m.input_dim, m.output_dim
+        pl.stride, pl.expand, pl.res = m.stride, m.expand, m.use_res_connect
+        ks, hid = pl.ks, pl.hid = list(m.kernel_sizes), list(m.channels)
+        branches = [list(op.children()) for op in (m.depth_ops if fused else m.ops)]
+        pl.nb = len(branches)
+        pl.se = fused and isinstance(m.se_op, mb.SqueezeAndExcitation)
+        if pl.nb == 0:
+            # an all-pruned block keeps only its (unused) pw_bn; give it ordinary slots
+            pl.HT = 0
+            self.bind_bn(m.pw_bn, self.bn_slots(oup), 0, oup)
+            return self._done(m, pl)
+        # expanding blocks keep their hidden tensors slab-major (segments = whole 16-channel slabs); the first block of the network (no
+        # expansion: hidden = input, narrow) stays plain with 8-channel padding
+        sp = pl.segpad = pads if m.expand else pad8
+        pl.seg, start = [], []
+        HT = total = 0
+        for h in hid:
+            pl.seg.append(HT)
+            start.append(total)
+            HT += sp(h)
+            total += h
+        pl.HT = HT
+        if fused:
+            pl.start, pl.total = start, total
+        wide = total if fused else HT                                     # width of the expand / projection masters
+        segs = list(zip(pl.seg, start if fused else pl.seg, hid))        # (padded offset, offset in the masters, channels)
+
+        so, pk, mods = {}, {}, dict(bne=[], bnd=[])
+        depth = 1 if m.expand else 0    # a branch's children: [expand ConvBNReLU | Narrow], depthwise ConvBNReLU[, projection conv]
+        if m.expand:
+            so["We"] = self.weight("dense", wide * inp)
+            so["bne"] = self.bn_slots(wide)
+        so["Wd"] = [self.weight("dw", sp(h) * k * k) for h, k in zip(hid, ks)]
+        so["bnd"] = self.bn_slots(HT)
+        so["Wp"] = self.weight("dense", oup * wide)
+        so["bnp"] = self.bn_slots(oup)
+
+        def bind_expand(cbr, at, c):
+            conv, bn, _ = cbr.children()
+            self.param(conv, "weight", so["We"] + at * inp, (c, inp, 1, 1))
+            self.bind_bn(bn, so["bne"], at, c)
+            mods["bne"].append(bn)
+
+        if fused and m.expand:
+            bind_expand(m.expand_conv, 0, total)
+        for ch, (sg, at, h), k, o_d in zip(branches, segs, ks, so["Wd"]):
+            if m.expand and not fused:
+                bind_expand(ch[0], at, h)
+            conv, bn, _ = ch[depth].children()
+            self.param(conv, "weight", o_d, (h, 1, k, k))
+            self.bind_bn(bn, so["bnd"], sg, h)
+            mods["bnd"].append(bn)
+            if not fused:
+                self.param(ch[-1], "weight", so["Wp"] + at, (oup, h, 1, 1), (HT, 1, 1, 1))
+        if fused:
+            pconv, out_bn = m.project_conv.children()
+            self.param(pconv, "weight", so["Wp"], (oup, total, 1, 1))
+        else:
+            out_bn = m.pw_bn
+        self.bind_bn(out_bn, so["bnp"], 0, oup)
+        mods["bnp"] = [out_bn]
+
+        if m.expand:
+            pieces = [(so["We"] + at * inp, h, inp, inp, sg, 0) for sg, at, h in segs] if fused else [(so["We"], HT, inp, inp, 0, 0)]
+            pk["We"], pk["WeT"] = self.pw_pack(HT, inp, pieces)
+        pieces = [(so["Wp"] + at, oup, h, total, 0, sg) for sg, at, h in segs] if fused else [(so["Wp"], oup, HT, HT, 0, 0)]
+        pk["Wp"], pk["WpT"] = self.pw_pack(oup, HT, pieces)
+        pk["taps"] = [self.dw_taps(o_d, sp(h), k * k) for o_d, h, k in zip(so["Wd"], hid, ks)]
+
+        if pl.se:
+            se = m.se_op
+            nh = pl.se_hid = se.n_hidden
+            for conv, key in ((se.se_reduce, "se1"), (se.se_expand, "se2")):
+                so[key + "w"] = self.weight("dense", conv.weight.numel())
+                so[key + "b"] = self.lp.take(conv.bias.numel())
+                self.param(conv, "weight", so[key + "w"], tuple(conv.weight.shape))
+                self.param(conv, "bias", so[key + "b"], tuple(conv.bias.shape))
+            # fp32 copies of the gate's dense layers over the padded channel layout, both with the channels contiguous:
+            # W1p[j][sg + c] = W1[j][st + c], W2t[j][sg + c] = W2[st + c][j], b2p[sg + c] = b2[st + c] (csrc/se.hip k_se_mlp)
+            o1, o2, o3 = pk["se"] = (self.lpf.take(nh * HT), self.lpf.take(nh * HT), self.lpf.take(HT))
+            for sg, at, h in segs:
+                self.jobsF.append((so["se1w"] + at, o1, nh, h, total, HT, sg, 0))
+                self.jobsF.append((so["se2w"] + at * nh, o2, h, nh, nh, HT, sg, 2))
+                self.jobsF.append((so["se2b"] + at, o3, 1, h, total, HT, sg, 0))
+        if fused:
+            # one weight-gradient GEMM per layer into a padded scratch matrix, folded into the contiguous tensors per segment
+            pl.fold_first, pl.fold_np, pl.fold_ne = len(self.fold_jobs), pl.nb, pl.nb if m.expand else 0
+            o_p = pl.Wp_scratch_off = self.lfw.take(oup * HT)
+            self.fold_jobs += [(o_p + sg, so["Wp"] + at, HT, total, oup, h) for sg, at, h in segs]
+            if m.expand:
+                o_e = pl.We_scratch_off = self.lfw.take(HT * inp)
+                self.fold_jobs += [(o_e + sg * inp, so["We"] + at * inp, h * inp, h * inp, 1, h * inp) for sg, at, h in segs]
+        self._done(m, pl, so=so, pk=pk, mods=mods, act=branches[0][depth][2])
+
+    def convbn(self, name, m):
+        conv, bn, act = m.children()
+        pl = SimplePlan()
+        pl.g_lo = self.lp.size
+        pl.name, pl.module = name, m
+        pl.cin, pl.cout, pl.k, pl.stride, pl.groups = conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.groups
+        C, Cp = conv.out_channels, pad8(conv.out_channels)
+        kk = conv.kernel_size[0] * conv.kernel_size[1]
+        cols = (conv.in_channels // conv.groups) * kk
+        so = dict(W=self.lp.take(Cp * cols), bn=self.bn_slots(Cp))
+        self.reg_slots.append(("dense" if conv.groups == 1 else "dw", so["W"], C * cols))
+        self.param(conv, "weight", so["W"], tuple(conv.weight.shape))
+        self.bind_bn(bn, so["bn"], 0, C)
+        pk = {}
+        if conv.groups == 1:
+            pk["W"], pk["WT"] = self.pw_pack(C, cols, [(so["W"], C, cols, cols, 0, 0)])
+        elif conv.groups == conv.in_channels == C:
+            pk["taps"] = self.dw_taps(so["W"], Cp, kk)
+        else:
+            raise NotImplementedError("grouped convolution other than depthwise")
+        self._done(m, pl, so=so, pk=pk, mods=dict(bn=[bn]), act=act)
+
+    def linear(self, name, m):
+        pl = SimplePlan()
+        pl.g_lo = self.lp.size
+        pl.name, pl.module = name, m
+        n, k = pl.cout, pl.cin = m.out_features, m.in_features
+        so = dict(W=self.weight("fc", n * k), b=self.lp.take(pad8(n)))
+        self.param(m, "weight", so["W"], (n, k))
+        if m.bias is not None:
+            self.reg_slots.append(("fcbias", so["b"], n))
+            self.param(m, "bias", so["b"], (n,))
+        pk = {}
+        pk["W"], pk["WT"] = self.pw_pack(n, k, [(so["W"], n, k, k, 0, 0)])
+        self._done(m, pl, so=so, pk=pk)
+
+
+def arena_layout(model, compute_dtype):
+    """The arena layout of `model` (on any device; nothing is allocated and no library call is made): one walk of the module tree."""
+    from .models import mobilenet_base as mb  # local import: avoids a cycle
+
+    lay = ArenaLayout(compute_dtype)
+    handled = set()
+    for name, m in model.named_modules():
+        if isinstance(m, (mb.InvertedResidualChannels, mb.InvertedResidualChannelsFused)):
+            walk = lay.block
+        elif isinstance(m, mb.ConvBNReLU) and id(m) not in handled:
+            walk = lay.convbn
+        elif isinstance(m, nn.Linear) and id(m) not in handled:
+            walk = lay.linear
+        else:
+            continue
+        handled.update(id(sub) for sub in m.modules())
+        walk(name, m)
+    # anything else that owns parameters (e.g. SE convs with bias) gets plain slots
+    for name, m in model.named_modules():
+        if id(m) in handled:
+            continue
+        for attr, p in list(m._parameters.items()):
+            if p is None:
+                continue
+            lay.param(m, attr, lay.lp.take(p.numel()), tuple(p.shape))
+        if isinstance(m, nn.BatchNorm2d):
+            raise NotImplementedError("BatchNorm2d outside ConvBNReLU / InvertedResidualChannels: %s" % name)
+    return lay
 
 
 class ArenaManager:
@@ -119,270 +390,35 @@ class ArenaManager:
     def device(self):
         return next(self.model.parameters()).device
 
-    # ------------------------------------------------------------------ layout
+    # ------------------------------------------------------------------ layout -> allocate -> migrate -> bind
     def materialize(self):
         """(Re)builds all arenas from the current module tree, migrating values, optimizer state and EMA shadows."""
-        from .models import mobilenet_base as mb  # local import: avoids a cycle
-
-        model = self.model
         dev = self.device
         if dev.type != "cuda":
             raise ops._lib.AtomnasHipError("the AtomNAS arenas live in HBM: move the model to the GPU first (model.cuda())")
-        self.compute_dtype = getattr(model, "compute_dtype", self.compute_dtype)
-        T = self.compute_dtype
+        self.compute_dtype = getattr(self.model, "compute_dtype", self.compute_dtype)
+        lay = arena_layout(self.model, self.compute_dtype)
+        new = self._allocate(lay.sizes, dev)
+        self._migrate(lay.binds, new, dev)
+        for key, arena in new.items():
+            setattr(self, key, arena)
+        self._bind(lay, dev)
 
-        lp, ls, lc = _Layout(), _Layout(), _Layout()   # params / bn stats / counters
-        lpk, lpf = _Layout(), _Layout()                # packed weights (T) / packed depthwise taps (fp32)
-        binds = []       # (tensor_getter, arena_name, off, shape, strides, setter)
-        reg_slots = []   # (kind, offset, numel) of weight slots for the L2 regulariser: dense / dw / fc / fcbias
-        pack_jobs_t, pack_jobs_f = [], []
-        plans = []
+    def _allocate(self, sizes, dev):
+        """zeroed arenas; the optimizer and EMA arenas only where an attached optimizer / EMA keeps such state"""
+        def zeros(n, wanted=True):
+            return torch.zeros(n, dtype=torch.float32, device=dev) if wanted else None
 
-        def bind_param(mod, attr, off, shape, strides=None):
-            binds.append(("P", mod, attr, off, tuple(shape), strides))
-
-        def bind_buf(mod, attr, arena, off, shape):
-            binds.append((arena, mod, attr, off, tuple(shape), None))
-
-        def pw_pack(src_off, rows, cols, src_ld):
-            """registers pack jobs for W[rows][cols] and its transpose; returns offsets/shapes in the T pack buffer"""
-            ldw, ldt = pad32(cols), pad32(rows)
-            o_w = lpk.take(pad64(rows) * ldw)
-            o_t = lpk.take(pad64(cols) * ldt)
-            pack_jobs_t.append((src_off, o_w, rows, cols, src_ld, ldw, 0, 0))
-            pack_jobs_t.append((src_off, o_t, rows, cols, src_ld, ldt, 0, 1))
-            return (o_w, pad64(rows), ldw), (o_t, pad64(cols), ldt)
-
-        def bn_slots(C):
-            return dict(g=lp.take(C), b=lp.take(C), rm=ls.take(C), rv=ls.take(C))
-
-        # ---- walk the module tree
-        handled = set()
-        for name, m in model.named_modules():
-            if isinstance(m, mb.InvertedResidualChannels):
-                pl = BlockPlan()
-                pl.g_lo = lp.size
-                pl.name = name
-                pl.module = m
-                nb = len(m.ops)
-                pl.inp, pl.oup, pl.stride, pl.expand = m.input_dim, m.output_dim, m.stride, m.expand
-                pl.res = m.use_res_connect
-                pl.ks = list(m.kernel_sizes)
-                pl.hid = list(m.channels)
-                pl.nb = nb
-                for sub in m.modules():
-                    handled.add(id(sub))
-                if nb == 0:
-                    pl.HT = 0
-                    # an all-pruned block keeps only its (unused) pw_bn; give it ordinary slots
-                    sl = bn_slots(pl.oup)
-                    self._bind_bn(bind_param, bind_buf, lc, m.pw_bn, sl, 0, pl.oup)
-                    pl.g_hi = lp.size; plans.append((m, pl, {}))
-                    continue
-                # expanding blocks keep their hidden tensors slab-major (segments = whole 16-channel slabs); the first block of
-                # the network (no expansion: hidden = input, narrow) stays plain with 8-channel padding
-                sp = pl.segpad = pads if m.expand else pad8
-                pl.seg = []
-                o = 0
-                for h in pl.hid:
-                    pl.seg.append(o)
-                    o += sp(h)
-                HT = pl.HT = o
-                so = {}
-                if m.expand:
-                    so["We"] = lp.take(HT * pl.inp)
-                    reg_slots.append(("dense", so["We"], HT * pl.inp))
-                    so["bne"] = bn_slots(HT)
-                so["Wd"] = [lp.take(sp(h) * k * k) for h, k in zip(pl.hid, pl.ks)]
-                for o_, h_, k_ in zip(so["Wd"], pl.hid, pl.ks):
-                    reg_slots.append(("dw", o_, sp(h_) * k_ * k_))
-                so["bnd"] = bn_slots(HT)
-                so["Wp"] = lp.take(pl.oup * HT)
-                reg_slots.append(("dense", so["Wp"], pl.oup * HT))
-                so["bnp"] = bn_slots(pl.oup)
-                idx_depth = 1 if m.expand else 0
-                for i, op in enumerate(m.ops):
-                    ch = list(op.children())
-                    s, h, k = pl.seg[i], pl.hid[i], pl.ks[i]
-                    if m.expand:
-                        conv, bn, _ = list(ch[0].children())
-                        bind_param(conv, "weight", so["We"] + s * pl.inp, (h, pl.inp, 1, 1))
-                        self._bind_bn(bind_param, bind_buf, lc, bn, so["bne"], s, h)
-                    conv, bn, _ = list(ch[idx_depth].children())
-                    bind_param(conv, "weight", so["Wd"][i], (h, 1, k, k))
-                    self._bind_bn(bind_param, bind_buf, lc, bn, so["bnd"], s, h)
-                    proj = ch[idx_depth + 1]
-                    bind_param(proj, "weight", so["Wp"] + s, (pl.oup, h, 1, 1), (HT, 1, 1, 1))
-                self._bind_bn(bind_param, bind_buf, lc, m.pw_bn, so["bnp"], 0, pl.oup)
-                # pack buffers
-                pk = {}
-                if m.expand:
-                    pk["We"], pk["WeT"] = pw_pack(so["We"], HT, pl.inp, pl.inp)
-                pk["Wp"], pk["WpT"] = pw_pack(so["Wp"], pl.oup, HT, HT)
-                pk["taps"] = []
-                for i, (h, k) in enumerate(zip(pl.hid, pl.ks)):
-                    o_f = lpf.take(k * k * sp(h))
-                    pack_jobs_f.append((so["Wd"][i], o_f, sp(h), k * k, k * k, sp(h), 0, 2))
-                    pk["taps"].append((o_f, k * k, sp(h)))
-                pl.g_hi = lp.size; plans.append((m, pl, dict(so=so, pk=pk)))
-            elif isinstance(m, mb.InvertedResidualChannelsFused):
-                # Fused block (models/mobilenet_base.py:145-274): ONE expand conv / BN over all `total` hidden channels, Narrow +
-                # depthwise per kernel size, optional SE, ONE projection conv + BN.  The kernels run on the same padded-segment
-                # layout as the branch block (HT = sum of segments padded to whole slabs); the total-wide parameters (expand
-                # weight / BN, projection weight, SE weights) are CONTIGUOUS masters in the arena, as the reference's state_dict
-                # has them, and reach the padded layout through per-segment pack jobs / per-segment finalize launches.
-                pl = BlockPlan()
-                pl.g_lo = lp.size
-                pl.name, pl.module, pl.fused = name, m, True
-                pl.inp, pl.oup, pl.stride, pl.expand = m.input_dim, m.output_dim, m.stride, m.expand
-                pl.res = m.use_res_connect
-                pl.ks, pl.hid = list(m.kernel_sizes), list(m.channels)
-                nb = pl.nb = len(m.depth_ops)
-                for sub in m.modules():
-                    handled.add(id(sub))
-                sp = pl.segpad = pads if m.expand else pad8
-                pl.seg, pl.start = [], []
-                o = st = 0
-                for h in pl.hid:
-                    pl.seg.append(o)
-                    pl.start.append(st)
-                    o += sp(h)
-                    st += h
-                HT, total = o, st
-                pl.HT, pl.total = HT, total
-                so, pk = {}, {}
-                ldw, ldt = pad32(pl.inp), pad32(HT)
-                if m.expand:
-                    conv, bn, _ = list(m.expand_conv.children())
-                    so["We"] = lp.take(total * pl.inp)
-                    reg_slots.append(("dense", so["We"], total * pl.inp))
-                    bind_param(conv, "weight", so["We"], (total, pl.inp, 1, 1))
-                    so["bne"] = bn_slots(total)
-                    self._bind_bn(bind_param, bind_buf, lc, bn, so["bne"], 0, total)
-                    o_w, o_t = lpk.take(pad64(HT) * ldw), lpk.take(pad64(pl.inp) * ldt)
-                    for sg, stt, h in zip(pl.seg, pl.start, pl.hid):
-                        pack_jobs_t.append((so["We"] + stt * pl.inp, o_w + sg * ldw, h, pl.inp, pl.inp, ldw, 0, 0))
-                        pack_jobs_t.append((so["We"] + stt * pl.inp, o_t + sg, h, pl.inp, pl.inp, ldt, 0, 1))
-                    pk["We"], pk["WeT"] = (o_w, pad64(HT), ldw), (o_t, pad64(pl.inp), ldt)
-                so["Wd"] = [lp.take(sp(h) * k * k) for h, k in zip(pl.hid, pl.ks)]
-                so["bnd"] = bn_slots(HT)
-                pk["taps"] = []
-                idx = 1 if m.expand else 0
-                for i, op in enumerate(m.depth_ops):
-                    conv, bn, _ = list(list(op.children())[idx].children())
-                    h, k = pl.hid[i], pl.ks[i]
-                    reg_slots.append(("dw", so["Wd"][i], sp(h) * k * k))
-                    bind_param(conv, "weight", so["Wd"][i], (h, 1, k, k))
-                    self._bind_bn(bind_param, bind_buf, lc, bn, so["bnd"], pl.seg[i], h)
-                    o_f = lpf.take(k * k * sp(h))
-                    pack_jobs_f.append((so["Wd"][i], o_f, sp(h), k * k, k * k, sp(h), 0, 2))
-                    pk["taps"].append((o_f, k * k, sp(h)))
-                pconv, pbn = list(m.project_conv.children())
-                so["Wp"] = lp.take(pl.oup * total)
-                reg_slots.append(("dense", so["Wp"], pl.oup * total))
-                bind_param(pconv, "weight", so["Wp"], (pl.oup, total, 1, 1))
-                so["bnp"] = bn_slots(pl.oup)
-                self._bind_bn(bind_param, bind_buf, lc, pbn, so["bnp"], 0, pl.oup)
-                ldp, ldpt = pad32(HT), pad32(pl.oup)
-                o_w, o_t = lpk.take(pad64(pl.oup) * ldp), lpk.take(pad64(HT) * ldpt)
-                for sg, stt, h in zip(pl.seg, pl.start, pl.hid):
-                    pack_jobs_t.append((so["Wp"] + stt, o_w, pl.oup, h, total, ldp, sg, 0))
-                    pack_jobs_t.append((so["Wp"] + stt, o_t, pl.oup, h, total, ldpt, sg, 1))
-                pk["Wp"], pk["WpT"] = (o_w, pad64(pl.oup), ldp), (o_t, pad64(HT), ldpt)
-                pl.se = isinstance(m.se_op, mb.SqueezeAndExcitation)
-                if pl.se:
-                    se = m.se_op
-                    pl.se_hid = se.n_hidden
-                    for conv_, key in ((se.se_reduce, "se1"), (se.se_expand, "se2")):
-                        so[key + "w"] = lp.take(conv_.weight.numel())
-                        so[key + "b"] = lp.take(conv_.bias.numel())
-                        reg_slots.append(("dense", so[key + "w"], conv_.weight.numel()))
-                        bind_param(conv_, "weight", so[key + "w"], tuple(conv_.weight.shape))
-                        bind_param(conv_, "bias", so[key + "b"], tuple(conv_.bias.shape))
-                    # fp32 copies of the gate's dense layers over the padded channel layout, both with the channels contiguous:
-                    # W1p[j][sg + c] = W1[j][st + c], W2t[j][sg + c] = W2[st + c][j], b2p[sg + c] = b2[st + c] (csrc/se.hip k_se_mlp)
-                    o1, o2, o3 = lpf.take(pl.se_hid * HT), lpf.take(pl.se_hid * HT), lpf.take(HT)
-                    for sg, stt, h in zip(pl.seg, pl.start, pl.hid):
-                        pack_jobs_f.append((so["se1w"] + stt, o1, pl.se_hid, h, total, HT, sg, 0))
-                        pack_jobs_f.append((so["se2w"] + stt * pl.se_hid, o2, h, pl.se_hid, pl.se_hid, HT, sg, 2))
-                        pack_jobs_f.append((so["se2b"] + stt, o3, 1, h, total, HT, sg, 0))
-                    pk["se"] = (o1, o2, o3)
-                pl.g_hi = lp.size; plans.append((m, pl, dict(so=so, pk=pk)))
-            elif isinstance(m, mb.ConvBNReLU) and id(m) not in handled:
-                conv, bn, _ = list(m.children())
-                for sub in m.modules():
-                    handled.add(id(sub))
-                pl = SimplePlan()
-                pl.g_lo = lp.size
-                pl.name, pl.module = name, m
-                pl.cin, pl.cout, pl.k, pl.stride, pl.groups = conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.groups
-                kk = conv.kernel_size[0] * conv.kernel_size[1]
-                cols = (conv.in_channels // conv.groups) * kk
-                so = dict(W=lp.take(pad8(conv.out_channels) * cols), bn=bn_slots(pad8(conv.out_channels)))
-                reg_slots.append(("dense" if conv.groups == 1 else "dw", so["W"], conv.out_channels * cols))
-                bind_param(conv, "weight", so["W"], tuple(conv.weight.shape))
-                self._bind_bn(bind_param, bind_buf, lc, bn, so["bn"], 0, conv.out_channels)
-                pk = {}
-                if conv.groups == 1:
-                    pk["W"], pk["WT"] = pw_pack(so["W"], conv.out_channels, cols, cols)
-                elif conv.groups == conv.in_channels == conv.out_channels:
-                    o_f = lpf.take(kk * pad8(conv.out_channels))
-                    pack_jobs_f.append((so["W"], o_f, pad8(conv.out_channels), kk, kk, pad8(conv.out_channels), 0, 2))
-                    pk["taps"] = (o_f, kk, pad8(conv.out_channels))
-                else:
-                    raise NotImplementedError("grouped convolution other than depthwise")
-                pl.g_hi = lp.size; plans.append((m, pl, dict(so=so, pk=pk)))
-            elif isinstance(m, nn.Linear) and id(m) not in handled:
-                handled.add(id(m))
-                pl = SimplePlan()
-                pl.g_lo = lp.size
-                pl.name, pl.module = name, m
-                pl.cin, pl.cout = m.in_features, m.out_features
-                so = dict(W=lp.take(m.out_features * m.in_features), b=lp.take(pad8(m.out_features)))
-                reg_slots.append(("fc", so["W"], m.out_features * m.in_features))
-                if m.bias is not None:
-                    reg_slots.append(("fcbias", so["b"], m.out_features))
-                bind_param(m, "weight", so["W"], (m.out_features, m.in_features))
-                if m.bias is not None:
-                    bind_param(m, "bias", so["b"], (m.out_features,))
-                pk = {}
-                pk["W"], pk["WT"] = pw_pack(so["W"], m.out_features, m.in_features, m.in_features)
-                pl.g_hi = lp.size; plans.append((m, pl, dict(so=so, pk=pk)))
-        # anything else that owns parameters (e.g. SE convs with bias) gets plain slots
-        for name, m in model.named_modules():
-            if id(m) in handled:
-                continue
-            for attr, p in list(m._parameters.items()):
-                if p is None:
-                    continue
-                bind_param(m, attr, lp.take(p.numel()), tuple(p.shape))
-            if isinstance(m, nn.BatchNorm2d):
-                raise NotImplementedError("BatchNorm2d outside ConvBNReLU / InvertedResidualChannels: %s" % name)
-
-        # ---- allocate
-        nP, nS, nC = max(lp.size, ALIGN), max(ls.size, ALIGN), max(lc.size, 8)
-        f32 = dict(dtype=torch.float32, device=dev)
-        newP = torch.zeros(nP, **f32)
-        newG = torch.zeros(nP, **f32)
-        newS = torch.zeros(nS, **f32)
-        newC = torch.zeros(nC, dtype=torch.int64, device=dev)
-        has_opt = len(self.optimizers) > 0
-        newSQ = torch.zeros(nP, **f32) if any(getattr(o, "needs_square_avg", True) for o in self.optimizers) else None
-        need_buf = has_opt and any(g["momentum"] > 0 for o in self.optimizers for g in o.param_groups)
-        newBUF = torch.zeros(nP, **f32) if need_buf else None
+        nP, nS = sizes["P"], sizes["S"]
+        square_avg = any(getattr(o, "needs_square_avg", True) for o in self.optimizers)
+        momentum = any(g["momentum"] > 0 for o in self.optimizers for g in o.param_groups)
         has_ema = len(self.emas) > 0
-        newEMA = torch.zeros(nP, **f32) if has_ema else None
-        newSEMA = torch.zeros(nS, **f32) if has_ema else None
+        return dict(P=zeros(nP), G=zeros(nP), S=zeros(nS), CNT=torch.zeros(sizes["CNT"], dtype=torch.int64, device=dev),
+                    SQ=zeros(nP, square_avg), BUF=zeros(nP, momentum), EMA=zeros(nP, has_ema), SEMA=zeros(nS, has_ema))
 
-        def view(arena, off, shape, strides):
-            if strides is None:
-                n = 1
-                for s in shape:
-                    n *= s
-                return arena[off:off + n].view(shape)
-            return torch.as_strided(arena, shape, strides, off)
-
-        # ---- migrate values and re-point tensors
+    def _migrate(self, binds, new, dev):
+        """Moves every value into its slot of the `new` arenas and re-points the modules' tensors, optimizer state and EMA shadows."""
+        model = self.model
         name_of = {id(p): n for n, p in model.named_parameters()}
         name_of.update({id(b): n for n, b in model.named_buffers()})
         self.param_slots = collections.OrderedDict()
@@ -408,24 +444,24 @@ class ArenaManager:
                     if arena_name == "P":
                         p = mod._parameters[attr]
                         nm = name_of.get(id(p))
-                        newv = view(newP, off, shape, strides)
+                        newv = _view(new["P"], off, shape, strides)
                         move(newv, p.data)
                         # optimizer state and EMA shadows follow the parameter
                         for opt in self.optimizers:
                             st = opt.state.get(p)
                             if st:
-                                for key, arena in (("square_avg", newSQ), ("momentum_buffer", newBUF)):
+                                for key, arena in (("square_avg", new["SQ"]), ("momentum_buffer", new["BUF"])):
                                     if key in st and arena is not None:
-                                        nv = view(arena, off, shape, strides)
+                                        nv = _view(arena, off, shape, strides)
                                         move(nv, st[key])
                                         st[key] = nv
                         for ema in self.emas:
                             if nm is not None and nm in ema._shadow:
-                                nv = view(newEMA, off, shape, strides)
+                                nv = _view(new["EMA"], off, shape, strides)
                                 move(nv, ema._shadow[nm])
                                 ema._shadow[nm] = nv
                         p.data = newv
-                        p.grad = view(newG, off, shape, strides)
+                        p.grad = _view(new["G"], off, shape, strides)
                         p._atomnas_off = off
                         p._atomnas_mgr = self
                         if nm is not None:
@@ -434,15 +470,15 @@ class ArenaManager:
                         b = mod._buffers[attr]
                         nm = name_of.get(id(b))
                         if arena_name == "S":
-                            newv = view(newS, off, shape, None)
+                            newv = _view(new["S"], off, shape, None)
                             move(newv, b)
                             for ema in self.emas:
                                 if nm is not None and nm in ema._shadow:
-                                    nv = view(newSEMA, off, shape, None)
+                                    nv = _view(new["SEMA"], off, shape, None)
                                     move(nv, ema._shadow[nm])
                                     ema._shadow[nm] = nv
                         else:
-                            newv = newC[off:off + 1].view(shape)
+                            newv = new["CNT"][off:off + 1].view(shape)
                             newv.copy_(b.to(dev))
                         mod._buffers[attr] = newv
                         if nm is not None:
@@ -453,34 +489,33 @@ class ArenaManager:
                 ops.gather_defer(False)   # the migration runs here (one launch), before anything reads the new arenas
             else:
                 ops.gather_flush()
-        self.P, self.G, self.S, self.CNT = newP, newG, newS, newC
-        self.SQ, self.BUF, self.EMA, self.SEMA = newSQ, newBUF, newEMA, newSEMA
-        self.nP, self.nS = nP, nS
-        self.reg_slots = reg_slots
 
-        # running_var padding = 1 so that eval-mode coefficients stay finite on padding channels
-        # (padding gamma is 0, so the value never matters)
-
-        # ---- pack buffers and job tables
-        self.packT = torch.zeros(max(lpk.size, ALIGN), dtype=T, device=dev)
-        self.packF = torch.zeros(max(lpf.size, ALIGN), dtype=torch.float32, device=dev)
-        self.jobsT = self._job_table(pack_jobs_t, dev)
-        self.jobsF = self._job_table(pack_jobs_f, dev)
-        self.njobsT, self.njobsF = len(pack_jobs_t), len(pack_jobs_f)
-
-        # ---- finish the plans (views)
+    def _bind(self, lay, dev):
+        """Pack buffers, job tables and the plans' views over the arenas just filled; the per-build state of the step."""
+        sizes = lay.sizes
+        self.nP, self.nS = sizes["P"], sizes["S"]
+        self.reg_slots = lay.reg_slots
+        self.packT = torch.zeros(sizes["packT"], dtype=self.compute_dtype, device=dev)
+        self.packF = torch.zeros(sizes["packF"], dtype=torch.float32, device=dev)
+        self.jobsT = _device_table(_PackJob, lay.jobsT, dev) if lay.jobsT else None
+        self.jobsF = _device_table(_PackJob, lay.jobsF, dev) if lay.jobsF else None
+        self.njobsT, self.njobsF = len(lay.jobsT), len(lay.jobsF)
         self.plans = {}
-        self._fold_build = []   # fold jobs of the fused blocks: (scratch offset, gradient-arena offset, src_ld, dst_ld, rows, cols)
-        self._fold_size = 0
-        for m, pl, info in plans:
+        for m, pl, info in lay.plans:
             pl.mgr = self
-            self._finish_plan(m, pl, info)
+            self._bind_plan(m, pl, info)
             object.__setattr__(m, "_plan", pl)
             self.plans[pl.name] = pl
-        self._build_fold_table(dev)
+        # fused blocks: padded scratch matrices of the expand / projection weight gradients and the table that folds them into the
+        # contiguous gradient tensors (ops.fold_jobs, csrc/reduce.hip k_fold_jobs)
+        self.FW = torch.zeros(sizes["FW"], dtype=torch.float32, device=dev)   # zero once: every fold clears what it read
+        self.fold_table, self.fold_blk0, rows = None, [0], []
+        for so, do, sld, dld, r, c in lay.fold_jobs:
+            rows.append((self.FW.data_ptr() + 4 * so, self.G.data_ptr() + 4 * do, sld, dld, r, c, self.fold_blk0[-1], 0))
+            self.fold_blk0.append(self.fold_blk0[-1] + (r * c + 255) // 256)
+        if rows:
+            self.fold_table = _device_table(_FoldJob, rows, dev)
 
-        # regulariser job tables (L2 'mnas' over conv/fc weights + classifier bias; L1 filled by the prune module)
-        self._build_reg_tables()
         for opt in self.optimizers:
             opt._on_materialize(self)
         for ema in self.emas:
@@ -512,211 +547,94 @@ class ArenaManager:
         if cb is not None:
             cb(pl)
 
-    def _bind_bn(self, bind_param, bind_buf, lc, bn, slots, seg, c):
-        if bn.affine:
-            bind_param(bn, "weight", slots["g"] + seg, (c,))
-            bind_param(bn, "bias", slots["b"] + seg, (c,))
-        if bn.track_running_stats:
-            bind_buf(bn, "running_mean", "S", slots["rm"] + seg, (c,))
-            bind_buf(bn, "running_var", "S", slots["rv"] + seg, (c,))
-            bind_buf(bn, "num_batches_tracked", "CNT", self._take_counter(lc), ())
+    def _bnv(self, sl, n, mods, C=None, **segmented):
+        """The dict the executors take for one BatchNorm slot group: views of `n` elements, C channels of which are the modules'."""
+        P, G, S = self.P, self.G, self.S
+        return dict(gamma=P[sl["g"]:sl["g"] + n], beta=P[sl["b"]:sl["b"] + n], dgamma=G[sl["g"]:sl["g"] + n],
+                    dbeta=G[sl["b"]:sl["b"] + n], rm=S[sl["rm"]:sl["rm"] + n], rv=S[sl["rv"]:sl["rv"] + n],
+                    C=n if C is None else C, mods=mods, mgr=self, **segmented)
 
     @staticmethod
-    def _take_counter(lc):
-        off = lc.size
-        lc.size += 1
-        return off
-
-    @staticmethod
-    def _job_table(jobs, dev):
-        if not jobs:
-            return None
-
-        class J(ctypes.Structure):
-            _fields_ = [("src_off", ctypes.c_long), ("dst_off", ctypes.c_long), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
-                        ("src_ld", ctypes.c_int), ("dst_ld", ctypes.c_int), ("c_off", ctypes.c_int), ("mode", ctypes.c_int)]
-
-        arr = (J * len(jobs))(*[J(*j) for j in jobs])
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-        return raw.to(dev)
-
-    def _vec(self, arena, off, n):
-        return arena[off:off + n]
-
-    def _finish_plan(self, m, pl, info):
-        from .functional import act_code
-        P, G, S = self.P, self.G, self.S
-        if isinstance(pl, BlockPlan) and getattr(pl, "fused", False):
-            self._finish_fused_plan(m, pl, info)
-            return
-        if isinstance(pl, BlockPlan):
-            pl.valid = True
-            pl.fused = pl.se = False
-            if pl.nb == 0:
-                return
-            so, pk = info["so"], info["pk"]
-            HT = pl.HT
-
-            def bnv(sl, C, mods):
-                d = dict(gamma=P[sl["g"]:sl["g"] + C], beta=P[sl["b"]:sl["b"] + C], dgamma=G[sl["g"]:sl["g"] + C],
-                         dbeta=G[sl["b"]:sl["b"] + C], rm=S[sl["rm"]:sl["rm"] + C], rv=S[sl["rv"]:sl["rv"] + C], C=C, mods=mods,
-                         mgr=self)
-                return d
-
-            idx_depth = 1 if pl.expand else 0
-            chs = [list(op.children()) for op in m.ops]
-            pl.act = act_code(list(chs[0][idx_depth].children())[2])
-            if pl.expand:
-                pl.We_grad = G[so["We"]:so["We"] + HT * pl.inp]
-                pl.bne = bnv(so["bne"], HT, [list(c[0].children())[1] for c in chs])
-                pl.We_pack = self._packview(pk["We"])
-                pl.WeT_pack = self._packview(pk["WeT"])
-            pl.Wd_grad = [G[o:o + pl.segpad(h) * k * k] for o, h, k in zip(so["Wd"], pl.hid, pl.ks)]
-            pl.bnd = bnv(so["bnd"], HT, [list(c[idx_depth].children())[1] for c in chs])
-            pl.Wp_grad = G[so["Wp"]:so["Wp"] + pl.oup * HT]
-            pl.bnp = bnv(so["bnp"], pl.oup, [m.pw_bn])
-            pl.Wp_pack = self._packview(pk["Wp"])
-            pl.WpT_pack = self._packview(pk["WpT"])
-            pl.taps = [self.packF[o:o + kk * c].view(kk, c) for (o, kk, c) in pk["taps"]]
-            # running_var of padding channels: 1
-            with torch.no_grad():
-                for sl, C in ((so.get("bne"), HT), (so["bnd"], HT)):
-                    if sl is None:
-                        continue
-                    rv = S[sl["rv"]:sl["rv"] + C]
-                    for s, h in zip(pl.seg, pl.hid):
-                        rv[s + h:s + pl.segpad(h)] = 1.0
-        else:
-            so, pk = info["so"], info["pk"]
-            if isinstance(m, nn.Linear):
-                pl.W_grad = G[so["W"]:so["W"] + pl.cout * pl.cin]
-                pl.bias = P[so["b"]:so["b"] + pad8(pl.cout)] if m.bias is not None else None
-                pl.bias_grad = G[so["b"]:so["b"] + pl.cout] if m.bias is not None else None
-                pl.W_pack = self._packview(pk["W"])
-                pl.WT_pack = self._packview(pk["WT"])
-            else:
-                conv, bn, actm = list(m.children())
-                pl.act = act_code(actm)
-                C = pl.cout
-                sl = so["bn"]
-                pl.bn = dict(gamma=P[sl["g"]:sl["g"] + pad8(C)], beta=P[sl["b"]:sl["b"] + pad8(C)], dgamma=G[sl["g"]:sl["g"] + pad8(C)],
-                             dbeta=G[sl["b"]:sl["b"] + pad8(C)], rm=S[sl["rm"]:sl["rm"] + pad8(C)], rv=S[sl["rv"]:sl["rv"] + pad8(C)],
-                             C=C, mods=[bn], mgr=self)
-                pl.W_grad = G[so["W"]:so["W"] + conv.weight.numel()]
-                if "W" in pk:
-                    pl.W_pack = self._packview(pk["W"])
-                    pl.WT_pack = self._packview(pk["WT"])
-                else:
-                    o, kk, c = pk["taps"]
-                    pl.taps = self.packF[o:o + kk * c].view(kk, c)
-                with torch.no_grad():
-                    pl.bn["rv"][C:] = 1.0
-
-    def _finish_fused_plan(self, m, pl, info):
-        from .functional import act_code
-        P, G, S = self.P, self.G, self.S
-        so, pk = info["so"], info["pk"]
-        HT, total = pl.HT, pl.total
-        pl.valid = True
-        segs = [(sg, st, h) for sg, st, h in zip(pl.seg, pl.start, pl.hid)]   # (padded offset, contiguous offset, channels)
-        # padded kernel channel -> index into the module's contiguous [total] vectors, -1 for the padding between branch segments
-        cmap = torch.full((HT,), -1, dtype=torch.int32)
-        for sg, st, h in segs:
-            cmap[sg:sg + h] = torch.arange(st, st + h, dtype=torch.int32)
-        pl.cmap = cmap.to(P.device)
-
-        def bnv(sl, C, mods, segmented):
-            d = dict(gamma=P[sl["g"]:sl["g"] + C], beta=P[sl["b"]:sl["b"] + C], dgamma=G[sl["g"]:sl["g"] + C],
-                     dbeta=G[sl["b"]:sl["b"] + C], rm=S[sl["rm"]:sl["rm"] + C], rv=S[sl["rv"]:sl["rv"] + C], C=C, mods=mods, mgr=self)
-            if segmented:   # contiguous [total] vectors, padded [HT] kernel layout
-                d["cmap"], d["Cpad"] = pl.cmap, HT
-            return d
-
-        idx = 1 if pl.expand else 0
-        dws = [list(op.children())[idx] for op in m.depth_ops]
-        pl.act = act_code(list(dws[0].children())[2])
-        if pl.expand:
-            pl.We_grad = G[so["We"]:so["We"] + total * pl.inp]
-            pl.bne = bnv(so["bne"], total, [list(m.expand_conv.children())[1]], True)
-            pl.We_pack, pl.WeT_pack = self._packview(pk["We"]), self._packview(pk["WeT"])
-        pl.Wd_grad = [G[o:o + pl.segpad(h) * k * k] for o, h, k in zip(so["Wd"], pl.hid, pl.ks)]
-        pl.bnd = bnv(so["bnd"], HT, [list(d.children())[1] for d in dws], False)
-        pl.Wp_grad = G[so["Wp"]:so["Wp"] + pl.oup * total]
-        # one weight-gradient GEMM per layer into a padded scratch matrix, folded into the contiguous tensors per segment
-        pl.fold_first = len(self._fold_build)
-        o_p = self._fold_take(pl.oup * HT)
-        pl.Wp_scratch_off = o_p
-        for sg, st, h in segs:
-            self._fold_build.append((o_p + sg, so["Wp"] + st, HT, total, pl.oup, h))
-        pl.fold_np = len(self._fold_build) - pl.fold_first
-        pl.fold_ne = 0
-        if pl.expand:
-            o_e = self._fold_take(HT * pl.inp)
-            pl.We_scratch_off = o_e
-            for sg, st, h in segs:
-                self._fold_build.append((o_e + sg * pl.inp, so["We"] + st * pl.inp, h * pl.inp, h * pl.inp, 1, h * pl.inp))
-            pl.fold_ne = len(self._fold_build) - pl.fold_first - pl.fold_np
-        pl.bnp = bnv(so["bnp"], pl.oup, [list(m.project_conv.children())[1]], False)
-        pl.Wp_pack, pl.WpT_pack = self._packview(pk["Wp"]), self._packview(pk["WpT"])
-        pl.taps = [self.packF[o:o + kk * c].view(kk, c) for (o, kk, c) in pk["taps"]]
+    def _unit_padding_var(bnv, spans):
+        """running_var of the padding channels [lo, hi) = 1, so that eval-mode coefficients stay finite there (padding gamma is 0, so
+        the value never matters)"""
         with torch.no_grad():
-            rv = S[so["bnd"]["rv"]:so["bnd"]["rv"] + HT]
-            for sg, h in zip(pl.seg, pl.hid):
-                rv[sg + h:sg + pl.segpad(h)] = 1.0
-        if pl.se:
-            n1, n2 = pl.se_hid * total, total * pl.se_hid
-            pl.se_w1, pl.se_b1 = P[so["se1w"]:so["se1w"] + n1], P[so["se1b"]:so["se1b"] + pl.se_hid]
-            pl.se_w2, pl.se_b2 = P[so["se2w"]:so["se2w"] + n2], P[so["se2b"]:so["se2b"] + total]
-            pl.se_dw1, pl.se_db1 = G[so["se1w"]:so["se1w"] + n1], G[so["se1b"]:so["se1b"] + pl.se_hid]
-            pl.se_dw2, pl.se_db2 = G[so["se2w"]:so["se2w"] + n2], G[so["se2b"]:so["se2b"] + total]
-            pl.se_act = act_code(m.se_op.active_fn)
-            o1, o2, o3 = pk["se"]
-            nh = pl.se_hid * HT
-            pl.se_w1p, pl.se_w2t, pl.se_b2p = self.packF[o1:o1 + nh], self.packF[o2:o2 + nh], self.packF[o3:o3 + HT]
-
-    # ---- fused blocks: padded scratch matrices of the expand / projection weight gradients and the table that folds them into the
-    # contiguous gradient tensors (ops.fold_jobs, csrc/reduce.hip k_fold_jobs)
-    def _fold_take(self, n):
-        off = self._fold_size
-        self._fold_size = _align(off + n)
-        return off
-
-    def _build_fold_table(self, dev):
-        jobs = self._fold_build
-        self.FW = torch.zeros(max(self._fold_size, ALIGN), dtype=torch.float32, device=dev)   # zero once: every fold clears what it read
-        self.fold_table, self.fold_blk0 = None, [0]
-        if not jobs:
-            return
-
-        class J(ctypes.Structure):
-            _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_ld", ctypes.c_long), ("dst_ld", ctypes.c_long),
-                        ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("blk0", ctypes.c_uint), ("pad_", ctypes.c_int)]
-
-        arr = (J * len(jobs))()
-        blk = 0
-        for q, (so, do, sld, dld, rows, cols) in enumerate(jobs):
-            arr[q] = J(self.FW.data_ptr() + 4 * so, self.G.data_ptr() + 4 * do, sld, dld, rows, cols, blk, 0)
-            blk += (rows * cols + 255) // 256
-            self.fold_blk0.append(blk)
-        self.fold_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(dev)
+            for lo, hi in spans:
+                bnv["rv"][lo:hi] = 1.0
 
     def _packview(self, t):
         off, rows, ld = t
         return self.packT[off:off + rows * ld].view(rows, ld)
 
-    # ------------------------------------------------------------------ regulariser tables
-    def _build_reg_tables(self):
-        """Job tables (offset, count, coefficient) for cal_l2_loss 'mnas'/'slimmable' (utils/optim.py:210-249)."""
-        self.l2_tables = {}
+    def _tapview(self, t):
+        off, kk, c = t
+        return self.packF[off:off + kk * c].view(kk, c)
 
+    def _bind_plan(self, m, pl, info):
+        from .functional import act_code
+        P, G = self.P, self.G
+        if isinstance(pl, BlockPlan):
+            pl.valid = True
+            if pl.nb == 0:
+                return
+        so, pk = info["so"], info["pk"]
+        if isinstance(m, nn.Linear):
+            pl.W_grad = G[so["W"]:so["W"] + pl.cout * pl.cin]
+            pl.bias = P[so["b"]:so["b"] + pad8(pl.cout)] if m.bias is not None else None
+            pl.bias_grad = G[so["b"]:so["b"] + pl.cout] if m.bias is not None else None
+            pl.W_pack, pl.WT_pack = self._packview(pk["W"]), self._packview(pk["WT"])
+            return
+        pl.act = act_code(info["act"])
+        mods = info["mods"]
+        if isinstance(pl, SimplePlan):   # ConvBNReLU
+            C, Cp = pl.cout, pad8(pl.cout)
+            pl.bn = self._bnv(so["bn"], Cp, mods["bn"], C=C)
+            pl.W_grad = G[so["W"]:so["W"] + m[0].weight.numel()]
+            if "W" in pk:
+                pl.W_pack, pl.WT_pack = self._packview(pk["W"]), self._packview(pk["WT"])
+            else:
+                pl.taps = self._tapview(pk["taps"])
+            self._unit_padding_var(pl.bn, [(C, Cp)])
+            return
+        HT, fused = pl.HT, pl.fused
+        wide = pl.total if fused else HT     # contiguous masters (fused) or padded segments (branch), see ArenaLayout.block
+        padding = [(s + h, s + pl.segpad(h)) for s, h in zip(pl.seg, pl.hid)]
+        segmented = {}
+        if fused:
+            # padded kernel channel -> index into the module's contiguous [total] vectors, -1 for the padding between branch segments
+            cmap = torch.full((HT,), -1, dtype=torch.int32)
+            for sg, st, h in zip(pl.seg, pl.start, pl.hid):
+                cmap[sg:sg + h] = torch.arange(st, st + h, dtype=torch.int32)
+            pl.cmap = cmap.to(P.device)
+            segmented = dict(cmap=pl.cmap, Cpad=HT)   # contiguous [total] vectors, padded [HT] kernel layout
+        if pl.expand:
+            pl.We_grad = G[so["We"]:so["We"] + wide * pl.inp]
+            pl.bne = self._bnv(so["bne"], wide, mods["bne"], **segmented)
+            pl.We_pack, pl.WeT_pack = self._packview(pk["We"]), self._packview(pk["WeT"])
+            if not fused:
+                self._unit_padding_var(pl.bne, padding)
+        pl.Wd_grad = [G[o:o + pl.segpad(h) * k * k] for o, h, k in zip(so["Wd"], pl.hid, pl.ks)]
+        pl.bnd = self._bnv(so["bnd"], HT, mods["bnd"])
+        self._unit_padding_var(pl.bnd, padding)
+        pl.Wp_grad = G[so["Wp"]:so["Wp"] + pl.oup * wide]
+        pl.bnp = self._bnv(so["bnp"], pl.oup, mods["bnp"])
+        pl.Wp_pack, pl.WpT_pack = self._packview(pk["Wp"]), self._packview(pk["WpT"])
+        pl.taps = [self._tapview(t) for t in pk["taps"]]
+        if pl.se:
+            total, nh = pl.total, pl.se_hid
+            n1, n2 = nh * total, total * nh
+            pl.se_w1, pl.se_b1 = P[so["se1w"]:so["se1w"] + n1], P[so["se1b"]:so["se1b"] + nh]
+            pl.se_w2, pl.se_b2 = P[so["se2w"]:so["se2w"] + n2], P[so["se2b"]:so["se2b"] + total]
+            pl.se_dw1, pl.se_db1 = G[so["se1w"]:so["se1w"] + n1], G[so["se1b"]:so["se1b"] + nh]
+            pl.se_dw2, pl.se_db2 = G[so["se2w"]:so["se2w"] + n2], G[so["se2b"]:so["se2b"] + total]
+            pl.se_act = act_code(m.se_op.active_fn)
+            o1, o2, o3 = pk["se"]
+            pl.se_w1p, pl.se_w2t, pl.se_b2p = self.packF[o1:o1 + nh * HT], self.packF[o2:o2 + nh * HT], self.packF[o3:o3 + HT]
+
+    # ------------------------------------------------------------------ regulariser tables
     def reg_table(self, entries):
         """entries: list of (offset, count, coef) -> device table for atomnas_reg_value / atomnas_reg_grad"""
-        class J(ctypes.Structure):
-            _fields_ = [("off", ctypes.c_long), ("count", ctypes.c_int), ("coef", ctypes.c_float)]
-
-        arr = (J * len(entries))(*[J(int(o), int(c), float(k)) for o, c, k in entries])
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-        return raw.to(self.device), len(entries)
+        return _device_table(_RegJob, [(int(o), int(c), float(k)) for o, c, k in entries], self.device), len(entries)
 
     # ------------------------------------------------------------------ per-step helpers
     def pack(self):
@@ -736,8 +654,6 @@ class ArenaManager:
         slot.copy_(self.hyper_host)
         self.hyper.copy_(slot, non_blocking=True)
 
-    # Outermost module call: refresh packed weights on entry; on exit bump every BN's num_batches_tracked once if any BN
-    # ran with batch statistics (all BNs of the model share their mode in the reference's train / calibration phases).
     # ---- per-step statistics workspace: every BatchNorm use of a step (forward and backward) takes a distinct slice of partial
     # rows.  The producing kernels write every row (include/atomnas_hip.h), so nothing is ever cleared.  A slice is dead as soon
     # as its finalize kernel has run, so re-using the workspace from the next top-level forward on is safe even when a
@@ -758,6 +674,8 @@ class ArenaManager:
             self._stats_ws = torch.empty(int(self._stats_need * 1.25) // 64 * 64 + 64, dtype=torch.float32, device=self.device)
         self._stats_off = 0
 
+    # Outermost module call: refresh packed weights on entry; on exit bump every BN's num_batches_tracked once if any BN
+    # ran with batch statistics (all BNs of the model share their mode in the reference's train / calibration phases).
     def enter(self):
         self.ensure()
         if self._depth == 0:
