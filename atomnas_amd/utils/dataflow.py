@@ -8,11 +8,14 @@ moved into a HIP kernel.
 Same iterator protocol as the reference's DataPrefetcher (__iter__ / __next__ / __len__, batch k + 1 in flight while batch k trains,
 `torch.cuda.current_stream().wait_stream(side)` at hand-over).  Decoding stays on the host, as in the reference: `dataset: imagenet1k`
 (image folders) decodes JPEG / PNG with PIL on loader threads (ImageFolderDecoded); LMDB records cannot be read here (no lmdb module).
-Loaders hand over decoded uint8 arrays, e.g. SyntheticDecodedImages below (bench.py --input-pipeline uint8).
+Loaders hand over decoded uint8 arrays, e.g. SyntheticDecodedImages below (bench.py --input-pipeline uint8).  `dataset: imagenet1k_store`
+(image_store.py) reads image folders that were decoded ONCE into flat uint8 shards: no decode per epoch, one staged copy per batch
+(DevicePrefetcher(staging=True)), or no pixel copy at all with the store resident in device memory (`dataset_resident: True`).
 """
 import ctypes
 import importlib
 import random
+import time
 
 import numpy as np
 import torch
@@ -127,6 +130,17 @@ def check_box(H, W, box, size):
     return h > MAX_SCALE * size or w > MAX_SCALE * size
 
 
+class ResidentImages(object):
+    """The `images` of a batch whose pixels are in device memory already (image_store.ResidentStore): `pool` the uint8 device tensor,
+    `offs` the byte offset of every sample in it, `sizes` their (H, W).  DevicePrefetcher copies no pixels for such a batch."""
+
+    def __init__(self, pool, offs, sizes):
+        self.pool, self.offs, self.sizes = pool, list(offs), list(sizes)
+
+    def __len__(self):
+        return len(self.offs)
+
+
 class DevicePrefetcher(object):
     """DataPrefetcher (utils/dataflow.py:13-58) for decoded uint8 samples.  `loader` yields batches (images, boxes, flips, targets):
     images = list of uint8 HWC tensors (pinned memory makes the copies asynchronous), boxes = list of (top, left, height, width),
@@ -144,10 +158,24 @@ class DevicePrefetcher(object):
     The host side of a batch -- drawing it from the loader (the crop / flip decisions of 256 samples), the descriptor table, 256 copy
     submissions: ~7 ms of Python -- runs in a worker thread (threaded=True, default), one batch ahead of the hand-over; the training
     thread only waits for an event.  Two slots (pixel pool, descriptors, output) alternate; a slot is refilled only after the consumer
-    of its previous batch has been ordered behind an event on the consumer's stream."""
+    of its previous batch has been ordered behind an event on the consumer's stream.
+
+    staging=True (host mode of a decoded image store, whose images are unpinned views of the page cache): the images of a batch are
+    packed into a per-slot PINNED staging buffer by `STAGE_THREADS` threads (numpy copies release the GIL) and ONE copy moves the packed
+    bytes to the device pool, instead of one pageable copy per image.  The staging buffer obeys the descriptors' rule: the host
+    rewrites it only after the slot's `desc_read` event, which is recorded behind the copy that reads it.  A crop-box batch stages only
+    the rows [bi, bi + bh) of every image and describes them as an image of height bh with bi = 0: k_image_preprocess and
+    k_image_resize_h (csrc/preprocess.hip) read the rows bi + ymin + y with ymin + y < bh -- pp_coeffs / PpWindow clamp the taps to
+    the crop box, as PIL crops before it resizes -- so no other row is ever read; whether a box is oversize is still decided on the
+    original size.  A window batch (Resize + CenterCrop reads the whole image) stages whole images.  staging=False (default) takes
+    exactly the launches, copies and allocations it always took.
+
+    Third batch form: `images` is a ResidentImages (image_store.ResidentLoader) -- the pool is the resident device tensor, desc.off the
+    resident offset, and no pixel copy is issued at all; only the tables and the targets travel."""
+    STAGE_THREADS = 4
 
     def __init__(self, loader, image_size=224, mean=T.IMAGENET_MEAN, std=T.IMAGENET_STD, max_image_bytes=3 * 640 * 640, threaded=True,
-                 filter="bilinear"):
+                 filter="bilinear", staging=False):
         if not torch.cuda.is_available():
             raise _lib.AtomnasHipError("DevicePrefetcher needs the GPU (the preprocessing kernel has no CPU fallback)")
         self.loader_len = len(loader) if hasattr(loader, "__len__") else None
@@ -163,6 +191,12 @@ class DevicePrefetcher(object):
         self.aug = [None, None]     # per slot: (device table, pinned table, int32 scratch of the colour pass) once a batch carries augs
         self.stage = [None, None]   # per slot: uint8 [N, S, S, 3], the resized batch the colour pass reads
         self.ws = [None, None]      # per slot: workspace of the two-pass path, allocated when a batch first holds an oversize crop box
+        self.staging = bool(staging)
+        self.pin = [None, None]     # per slot: pinned staging buffer of the packed pixels (staging=True), under the desc_read rule
+        self._stagers = None        # thread pool of the staging copies
+        # where _submit's host time went (tools/bench_feed.py): drawing the batch from the loader, waiting for the slot's desc_read event
+        # (the device is behind: idle time, not work), writing the tables, packing the staging buffer, queueing copies and launches
+        self.host_seconds = {"draw": 0.0, "wait": 0.0, "tables": 0.0, "stage": 0.0, "queue": 0.0}
         # per slot: event behind the last host-to-device copy that READ the slot's pinned descriptors.  The host rewrites them for the
         # batch after next; nothing else orders the host against that copy (the reference's prefetcher never reuses host staging
         # memory), and a caller that does not synchronise per step (graph replay) runs several steps ahead of the device.
@@ -183,10 +217,10 @@ class DevicePrefetcher(object):
         else:
             self._pending = self._submit()
 
-    def _slot(self, q, n, nbytes):
+    def _slot(self, q, n, nbytes, pool=True):
         s = self.slots[q]
         if s is None or s[0].numel() < nbytes or s[3].shape[0] != n:
-            cap = max(nbytes, n * self.max_image_bytes // 4)
+            cap = max(nbytes, n * self.max_image_bytes // 4) if pool else 0   # (a resident batch brings its pool along)
             # descriptors, then the int32 batch positions of the oversize images (at most n)
             s = (torch.empty(cap, dtype=torch.uint8, device="cuda"), torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8, device="cuda"),
                  torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8).pin_memory(),
@@ -197,26 +231,44 @@ class DevicePrefetcher(object):
     def _submit(self):
         """draws the next batch and queues its copies and the preprocessing launch on the side stream -> (input, target, ready event)
         or None at the end of the loader"""
+        t0 = time.perf_counter()
         try:
             batch = next(self.loader)
         except StopIteration:
             return None
+        t1 = time.perf_counter()
         images, boxes, flips, target = batch[:4]
         augs = batch[4] if len(batch) > 4 else None
         if augs is not None and all(a is None for a in augs):
             augs = None
         q = self.k & 1
         n = len(images)
-        sizes = [int(im.numel()) for im in images]
-        offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-        pool, desc_dev, desc_pin, out = self._slot(q, n, int(offs[-1]))
-        ev = self.desc_read[q]
-        if ev is not None:
-            ev.synchronize()   # the copy queued two batches ago has read desc_pin (normally long done: no wait in steady state)
-        d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE, count=n)
-        large = []
         window = augs is not None and any(a is not None and a.resize is not None for a in augs)
         colour = augs is not None and any(a is not None and (a.ops or a.inc is not None) for a in augs)
+        resident = isinstance(images, ResidentImages)
+        rows = None   # staged crop-box batch: (first row, row count) of every image that travels
+        if resident:
+            hw, offs = images.sizes, images.offs
+            pool, (_, desc_dev, desc_pin, out) = images.pool, self._slot(q, n, 0, pool=False)
+        else:
+            hw = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+            sizes = [int(im.numel()) for im in images]
+            if self.staging and not window:
+                for (H, W), box in zip(hw, boxes):
+                    check_box(H, W, box, self.size)   # (a box outside its image is refused before it sizes anything)
+                rows = [(int(box[0]), int(box[2])) for box in boxes]
+                sizes = [bh * W * 3 for (H, W), (bi, bh) in zip(hw, rows)]
+            offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
+            pool, desc_dev, desc_pin, out = self._slot(q, n, int(offs[-1]))
+        ev = self.desc_read[q]
+        tw = time.perf_counter()
+        if ev is not None:
+            # the copy queued two batches ago has read desc_pin (and the staging buffer).  A consumer that does not synchronise per step
+            # runs ahead of the device, and so does this thread: here is where it waits for the device (host_seconds['wait'])
+            ev.synchronize()
+        tw = time.perf_counter() - tw
+        d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE, count=n)
+        large = []
         if window and not all(a is not None and a.resize is not None for a in augs):
             raise ValueError("a batch mixes resize-window and crop-box samples")
         if augs is not None:
@@ -226,27 +278,37 @@ class DevicePrefetcher(object):
                                torch.empty(n, dtype=torch.int32, device="cuda"))
             aug_dev, aug_pin, means = self.aug[q]
             a = np.frombuffer(aug_pin.numpy(), dtype=AUG_DTYPE, count=n)
-        for i, (im, box, fl) in enumerate(zip(images, boxes, flips)):
-            H, W = int(im.shape[0]), int(im.shape[1])
+        for i, ((H, W), box, fl) in enumerate(zip(hw, boxes, flips)):
             if window:
                 if check_window(H, W, augs[i].resize):
                     large.append(i)
                 box_d = (0, 0, H, W)   # (not read by the window mode)
             else:
-                if check_box(H, W, box, self.size):
+                if check_box(H, W, box, self.size):   # (the ORIGINAL size decides, also where only the box's rows travel)
                     large.append(i)
                 box_d = box
+            if rows is not None:
+                H, box_d = rows[i][1], (0, box_d[1], box_d[2], box_d[3])
             d[i] = (int(offs[i]), H, W, box_d[0], box_d[1], box_d[2], box_d[3], 1 if fl else 0, 0)
             if augs is not None:
                 fill_aug(a[i], augs[i], box, self.size)
         if large:
             np.frombuffer(desc_pin.numpy(), dtype=np.int32, count=len(large), offset=n * DESC_DTYPE.itemsize)[:] = large
-            max_rows = max(int(images[i].shape[0]) if window else int(boxes[i][2]) for i in large)
+            max_rows = max(hw[i][0] if window else int(boxes[i][2]) for i in large)
+        t2 = time.perf_counter()
+        staged = self.staging and not resident
+        if staged:   # behind the desc_read wait above: the copy that read this slot's staging buffer two batches ago is done
+            total = int(offs[-1])
+            pin = self._stage(q, images, rows, offs, sizes, pool.numel())
+        t3 = time.perf_counter()
         with torch.cuda.stream(self.stream):
             if self.consumed[q] is not None:
                 self.stream.wait_event(self.consumed[q])   # the slot's previous batch has been consumed (handed out two batches ago)
-            for i, im in enumerate(images):
-                pool[int(offs[i]):int(offs[i]) + sizes[i]].copy_(im.reshape(-1), non_blocking=True)
+            if staged:
+                pool[:total].copy_(pin[:total], non_blocking=True)   # in front of the desc_read event below
+            elif not resident:
+                for i, im in enumerate(images):
+                    pool[int(offs[i]):int(offs[i]) + sizes[i]].copy_(im.reshape(-1), non_blocking=True)
             desc_dev.copy_(desc_pin, non_blocking=True)
             if augs is not None:
                 aug_dev[:n * AUG_DTYPE.itemsize].copy_(aug_pin[:n * AUG_DTYPE.itemsize], non_blocking=True)   # in front of the event below
@@ -278,7 +340,30 @@ class DevicePrefetcher(object):
             ready = torch.cuda.Event()
             ready.record(self.stream)
         self.k += 1
+        hs, t4 = self.host_seconds, time.perf_counter()
+        hs["draw"], hs["wait"], hs["tables"] = hs["draw"] + t1 - t0, hs["wait"] + tw, hs["tables"] + t2 - t1 - tw
+        hs["stage"], hs["queue"] = hs["stage"] + t3 - t2, hs["queue"] + t4 - t3
         return out, tgt, ready
+
+    def _stage(self, q, images, rows, offs, sizes, capacity):
+        """packs the batch's images (`rows`: only those rows of each) into the slot's pinned staging buffer at `offs` -> the buffer"""
+        pin = self.pin[q]
+        if pin is None or pin.numel() < capacity:
+            pin = self.pin[q] = torch.empty(capacity, dtype=torch.uint8).pin_memory()
+        if self._stagers is None:
+            import concurrent.futures
+            self._stagers = concurrent.futures.ThreadPoolExecutor(max_workers=self.STAGE_THREADS, thread_name_prefix="atomnas-stage")
+        host = pin.numpy()
+
+        def copy(part):
+            for i in range(part, len(images), self.STAGE_THREADS):
+                src = images[i].numpy()
+                if rows is not None:
+                    src = src[rows[i][0]:rows[i][0] + rows[i][1]]
+                np.copyto(host[int(offs[i]):int(offs[i]) + sizes[i]], src.reshape(-1))
+
+        list(self._stagers.map(copy, range(self.STAGE_THREADS)))   # (re-raises what a copy raised)
+        return pin
 
     def _work(self):
         torch.cuda.set_device(self.device)
@@ -347,6 +432,10 @@ class DevicePrefetcher(object):
         self._pending = None
         self.stream.synchronize()
         self.slots, self.ws, self.aug, self.stage = [None, None], [None, None], [None, None], [None, None]
+        self.pin = [None, None]
+        if self._stagers is not None:
+            self._stagers.shutdown()
+            self._stagers = None
 
     def __del__(self):
         try:
@@ -607,6 +696,12 @@ def dataset(train_transforms, val_transforms, test_transforms, FLAGS):
         train_set = (ImageFolderDecoded(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms)
                      if (not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)) else None)
         return train_set, ImageFolderDecoded(os.path.join(FLAGS.dataset_dir, 'val'), val_transforms), None
+    if name == 'imagenet1k_store':   # the image folders of 'imagenet1k', decoded once by tools/make_image_store.py
+        import os
+        from .image_store import DecodedStore
+        train_set = (DecodedStore(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms)
+                     if (not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)) else None)
+        return train_set, DecodedStore(os.path.join(FLAGS.dataset_dir, 'val'), val_transforms), None
     if name == 'imagenet1k_lmdb':
         raise NotImplementedError("dataset 'imagenet1k_lmdb': the lmdb module is not in this image (utils/lmdb_dataset.py:24-71); the same "
                                   "records decode through ImageFolderDecoded's PIL path once they can be read -- use 'imagenet1k' (image folders)")
@@ -670,6 +765,25 @@ class DecodedLoader(object):
             yield ([s[0] for s in samples], [s[1] for s in samples], [s[2] for s in samples], (target.pin_memory() if pin else target)) + extra
 
 
+def _resident_loaders(train_set, val_set, FLAGS, rank, world, training, calibrating, seed):
+    """data_loader's four loaders for `dataset_resident: True`: every split the run uses is a rank share in device memory
+    (image_store.ResidentStore, uploaded when a loader is first iterated); the calibration loader shares the train upload.  The same
+    shuffle flags as the host loaders; with world > 1 the shares are fixed for the run (image_store.ResidentLoader)."""
+    from .image_store import DecodedStore, ResidentLoader, ResidentStore
+    for dset in (train_set if (training or calibrating) else None, val_set):
+        if dset is not None and not isinstance(dset, DecodedStore):
+            raise ValueError("dataset_resident: True needs a decoded image store (dataset: imagenet1k_store), not %s" % type(dset).__name__)
+    reserve = float(FLAGS.get('dataset_resident_reserve_gb', 32))
+    drop_last = FLAGS.get('drop_last', False)
+    train_res = ResidentStore(train_set, rank, world, seed, reserve) if (training or calibrating) else None
+    train_loader = ResidentLoader(train_res, FLAGS._loader_batch_size, True, drop_last, seed) if training else None
+    calib_loader = (ResidentLoader(train_res, FLAGS.get('_loader_batch_size_calib', FLAGS._loader_batch_size), True, drop_last, seed)
+                    if calibrating else None)
+    val_loader = ResidentLoader(ResidentStore(val_set, rank, world, seed, reserve), FLAGS._loader_batch_size,
+                                bool(FLAGS.use_distributed), drop_last, seed)
+    return train_loader, calib_loader, val_loader, val_loader
+
+
 def data_loader(train_set, val_set, test_set, FLAGS):
     """Get data loader (utils/dataflow.py:214-267) -> (train_loader, calib_loader, val_loader, test_loader).  `data_loader_workers`:
     decode threads of a loader (at most 16; the reference's worker processes also crop / resize / normalize, which is GPU work here)."""
@@ -687,6 +801,8 @@ def data_loader(train_set, val_set, test_set, FLAGS):
     calibrating = bool(FLAGS.get('bn_calibration', False))
     seed = int(FLAGS.get('random_seed', 0))
     workers = min(16, int(FLAGS.get('data_loader_workers', 0) or 0))
+    if FLAGS.get('dataset_resident', False):
+        return _resident_loaders(train_set, val_set, FLAGS, rank or 0, world or 1, training, calibrating, seed)
 
     def _build_loader(dset, batch_size, shuffle):
         # distributed: the sampler shuffles (DistributedSampler's default) and the loader does not; single process: the loader does

@@ -35,7 +35,9 @@ def device_batches(loader, steps):
     from atomnas_amd.utils import dataflow
     tf = getattr(getattr(loader, 'dset', None), 'transform', None)   # the split's DeviceTransform: resampling filter, mean, std
     kw = dict(filter=tf.filter, mean=tf.mean, std=tf.std) if isinstance(tf, dataflow.DeviceTransform) else {}
-    pre = dataflow.DevicePrefetcher(loader, image_size=cfg.FLAGS.image_size, **kw)
+    from atomnas_amd.utils.image_store import DecodedStore
+    # a decoded store hands out unpinned views of the page cache: one staged copy per batch instead of one pageable copy per image
+    pre = dataflow.DevicePrefetcher(loader, image_size=cfg.FLAGS.image_size, staging=isinstance(getattr(loader, 'dset', None), DecodedStore), **kw)
     try:
         for i, (x, y) in enumerate(pre):
             if steps is not None and i >= steps:
