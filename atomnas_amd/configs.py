@@ -1,9 +1,12 @@
 """Named model / hyper-parameter sets of the reference's yaml tree, as Python data (for bench.py, smoke and tests that
-must not read /root/reference).  Values: apps/mobilenet/models/fix_first/supernet_single_path_nas*.yml,
+must not read /root/reference).  Values: apps/mobilenet/models/fix_first/supernet_single_path_nas*.yml, .../supernet_mixconv_relu.yml,
 apps/mobilenet/models/mobilenet_v2_1.0*.yml, apps/slimming/shrink/atomnas_{a,c}.yml, apps/mobilenet/default_mnas_scheduler.yml."""
 
 _SUPERNET_ROWS = [[1, 16, 1, 1, [3]], [6, 24, 4, 2, [3, 5, 7]], [6, 40, 4, 2, [3, 5, 7]], [6, 80, 4, 2, [3, 5, 7]],
                   [6, 96, 4, 1, [3, 5, 7]], [6, 192, 4, 2, [3, 5, 7]], [6, 320, 1, 1, [3, 5, 7]]]
+# the AtomNAS-C supernet with MixConv-size atoms: apps/mobilenet/models/fix_first/supernet_mixconv_relu.yml
+_MIX_KS = [3, 5, 7, 9, 11]
+_MIX_SUPERNET_ROWS = [list(r[:4]) + [list(_MIX_KS) if len(r[4]) > 1 else list(r[4])] for r in _SUPERNET_ROWS]
 _MBV2_ROWS = [[1, 16, 1, 1, [3]], [6, 24, 2, 2, [3]], [6, 32, 3, 2, [3]], [6, 64, 4, 2, [3]], [6, 96, 3, 1, [3]],
               [6, 160, 3, 2, [3]], [6, 320, 1, 1, [3]]]
 
@@ -41,6 +44,8 @@ def model_kwparams(name):
         return dict(base, input_channel=32, inverted_residual_setting=[list(r) for r in _SUPERNET_ROWS])
     if name == 'atomnas_a_supernet':
         return dict(base, input_channel=16, inverted_residual_setting=[list(r) for r in _SUPERNET_ROWS])
+    if name == 'atomnas_mix_supernet':
+        return dict(base, input_channel=32, inverted_residual_setting=[list(r) for r in _MIX_SUPERNET_ROWS])
     if name == 'mobilenet_v2_1.0':
         return dict(base, input_channel=32, inverted_residual_setting=[list(r) for r in _MBV2_ROWS])
     raise KeyError(name)

@@ -1,4 +1,5 @@
-// Depthwise k x k convolution (k in {3,5,7}, stride in {1,2}, pad (k-1)/2) for NHWC activations on gfx950.
+// Depthwise k x k convolution (k in {3,5,7,9,11}, stride in {1,2}, pad (k-1)/2) for NHWC activations on gfx950.  The kernels of this
+// file are those of k <= 7; k = 9 / 11 run the kernels of dwconv_big.hip behind the same C entries (below).
 //
 // Replaces the ATen call behind  nn.Conv2d(hid, hid, k, stride, pad, groups=hid, bias=False)  in the reference's
 // atomic block (models/mobilenet_base.py:330-336 via ConvBNReLU :120-142), forward and backward, and fuses the
@@ -971,6 +972,7 @@ namespace atomnas {
 // THE order of the kernel families; the first plan that accepts runs.  (Each plan declines what is not its own: mm2 takes the stride-2
 // forward only, mm stride 1 only, cw stride 1 and the stride-2 backward.)  The tile kernels of this file take everything else.
 DwFamily dw_pick(const DwShape& s, int dir, DwPlan& p) {
+  if (s.k > 7) return big_plan(s, dir, p) ? DW_BIG : DW_TILE;   // k = 9 / 11: a family of their own, the plans below are never asked
   if (mm2_plan(s, dir, p)) return DW_MM2;
   if (mm_plan(s, dir, p)) return DW_MM;
   if (cw_plan(s, dir, p)) return DW_CW;
@@ -1002,7 +1004,7 @@ extern "C" int atomnas_dwconv_fwd(const void* x, int ldx, long x_ss, const float
                                   const float* w, int ldw, void* y, int ldy, long y_ss, float* stats, int stat_ld, int stat_rows, int N, int H, int W,
                                   int C, int k, int stride, int dtype, void* stream) {
   ATOMNAS_REQUIRE(x && w && y, "dwconv_fwd: null pointer");
-  ATOMNAS_REQUIRE((k == 3 || k == 5 || k == 7) && (stride == 1 || stride == 2), "dwconv_fwd: unsupported k=%d stride=%d", k, stride);
+  ATOMNAS_REQUIRE((k == 3 || k == 5 || k == 7 || k == 9 || k == 11) && (stride == 1 || stride == 2), "dwconv_fwd: unsupported k=%d stride=%d", k, stride);
   ATOMNAS_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv_fwd: bad dtype %d", dtype);
   ATOMNAS_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "dwconv_fwd: empty shape");
   const int cpad = (C + 7) / 8 * 8;
@@ -1022,8 +1024,10 @@ extern "C" int atomnas_dwconv_fwd(const void* x, int ldx, long x_ss, const float
     case DW_MM2: return mm2_launch_fwd(p, a);
     case DW_MM: return mm_launch_fwd(p, a);
     case DW_CW: return cw_launch_fwd(p, a);
+    case DW_BIG: return big_launch_fwd(p, a);
     case DW_TILE: break;
   }
+  ATOMNAS_REQUIRE(k <= 7, "dwconv_fwd: no tile for k=%d fits the LDS of this device", k);
   return tile_dispatch(a.s, [&](auto tt, auto kc, auto sc) {
     return tile_launch_fwd<typename decltype(tt)::type, decltype(kc)::value, decltype(sc)::value>(a);
   });
@@ -1035,7 +1039,7 @@ extern "C" int atomnas_dwconv_bwd(const void* g, int ldg, long g_ss, const void*
                                   int part_rows, float* dw_ws, int N, int H, int W, int C, int k, int stride, int dtype,
                                   void* stream) {
   ATOMNAS_REQUIRE(g && x && w && h, "dwconv_bwd: null pointer");
-  ATOMNAS_REQUIRE((k == 3 || k == 5 || k == 7) && (stride == 1 || stride == 2), "dwconv_bwd: unsupported k=%d stride=%d", k, stride);
+  ATOMNAS_REQUIRE((k == 3 || k == 5 || k == 7 || k == 9 || k == 11) && (stride == 1 || stride == 2), "dwconv_bwd: unsupported k=%d stride=%d", k, stride);
   ATOMNAS_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv_bwd: bad dtype %d", dtype);
   ATOMNAS_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "dwconv_bwd: empty shape");
   const int cpad = (C + 7) / 8 * 8;
@@ -1055,8 +1059,10 @@ extern "C" int atomnas_dwconv_bwd(const void* g, int ldg, long g_ss, const void*
   switch (dw_pick(a.s, 1, p)) {
     case DW_MM: return mm_launch_bwd(p, a);
     case DW_CW: return cw_launch_bwd(p, a);
+    case DW_BIG: return big_launch_bwd(p, a);
     default: break;   // (no backward in the mm2 family)
   }
+  ATOMNAS_REQUIRE(k <= 7, "dwconv_bwd: no tile for k=%d fits the LDS of this device", k);
   return tile_dispatch(a.s, [&](auto tt, auto kc, auto sc) {
     return tile_launch_bwd<typename decltype(tt)::type, decltype(kc)::value, decltype(sc)::value>(a);
   });

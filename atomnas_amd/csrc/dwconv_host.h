@@ -1,4 +1,4 @@
-// Host side of the depthwise sources (dwconv.hip: tile kernels and the C entries; dwconv_cw.hip, dwconv_mm.hip, dwconv_mm2.hip;
+// Host side of the depthwise sources (dwconv.hip: tile kernels and the C entries; dwconv_cw.hip, dwconv_mm.hip, dwconv_mm2.hip, dwconv_big.hip;
 // csrc/experimental/xdw_cw_bwd.hip for the geometry): the argument structs behind the C entries, the run-time switches, one plan per
 // launch (family order, accept / reject, launch sizing), the tile geometry of the channel-pair kernels and the dispatch helpers.
 // The device side they share is dwconv_cw.h.
@@ -61,11 +61,20 @@ inline const DwEnv& dw_env() {
 // One plan per launch.  <family>_plan is the COMPLETE accept / reject decision for a shape and direction (dir 0 forward, 1 backward:
 // switch bits, layout, geometry, LDS limit) and leaves the geometry and the LDS size in the plan; <family>_launch_* runs an accepted
 // plan and cannot decline.  dw_pick (dwconv.hip) states the order of the families; the C entries and the *_supported queries share it.
-enum DwFamily { DW_TILE, DW_CW, DW_MM, DW_MM2 };
+enum DwFamily { DW_TILE, DW_CW, DW_MM, DW_MM2, DW_BIG };
+// geometry of the k = 9 / 11 kernels (dwconv_big.hip): 16-channel slabs, tiles of TH x TW pixels, haloed LDS window
+struct BigGeom {
+  int N, H, W, C, Ho, Wo;
+  int TH, TW;             // tile: output pixels (forward) / input pixels (backward); TW a multiple of 4, backward TH even
+  int tiles_y, tiles_x;   // tiles per image
+  int LH, LW, RP;         // LDS window: rows, columns, row pitch (floats)
+  int nworkers, nslabs;
+};
 struct DwPlan {
   CwGeom g;
   MmGeom mg;     // DW_MM
   Mm2Geom mg2;   // DW_MM2
+  BigGeom bg;    // DW_BIG
   size_t lds;
 };
 bool cw_plan(const DwShape& s, int dir, DwPlan& p);     // dwconv_cw.hip: packed-FMA tap rows, stride 1 both ways, stride 2 backward
@@ -76,6 +85,9 @@ int mm_launch_fwd(const DwPlan& p, const DwFwdArgs& a);
 int mm_launch_bwd(const DwPlan& p, const DwBwdArgs& a);
 bool mm2_plan(const DwShape& s, int dir, DwPlan& p);    // dwconv_mm2.hip: the stride-2 forward on the matrix cores, bf16
 int mm2_launch_fwd(const DwPlan& p, const DwFwdArgs& a);
+bool big_plan(const DwShape& s, int dir, DwPlan& p);    // dwconv_big.hip: k = 9 / 11, every stride, storage type and layout
+int big_launch_fwd(const DwPlan& p, const DwFwdArgs& a);
+int big_launch_bwd(const DwPlan& p, const DwBwdArgs& a);
 DwFamily dw_pick(const DwShape& s, int dir, DwPlan& p);
 
 static bool cw_geometry(CwGeom& g, int N, int H, int W, int C, int K) {
@@ -175,7 +187,7 @@ static unsigned cw_grid(const CwGeom& g) {
 // ---- one copy of each dispatch idiom: f receives the choice as a compile-time constant
 template <int V> using IC = std::integral_constant<int, V>;
 template <typename T> struct DwType { typedef T type; };
-template <typename F> static auto dw_for_k(int k, F&& f) {
+template <typename F> static auto dw_for_k(int k, F&& f) {   // the tile kernels' k; k > 7 never comes here (DW_BIG)
   if (k == 3) return f(IC<3>{});
   if (k == 5) return f(IC<5>{});
   return f(IC<7>{});

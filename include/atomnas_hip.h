@@ -65,7 +65,7 @@ int atomnas_abi_version(void);
 int atomnas_runtime_version(void);
 
 /* ---- depthwise k x k convolution: nn.Conv2d(C, C, k, stride, (k-1)/2, groups=C, bias=False)
- *      models/mobilenet_base.py:330-336 (built through ConvBNReLU :120-142); k in {3,5,7}, stride in {1,2}.
+ *      models/mobilenet_base.py:330-336 (built through ConvBNReLU :120-142); k in {3,5,7,9,11}, stride in {1,2}.
  * forward: y = dwconv(act(x*in_scale+in_shift));  stats rows [sum y, sum y^2] for channels 0..C-1   (in_scale == NULL: x as is)
  *   w: fp32 taps [k*k][ldw] (tap-major, see atomnas_pack_weights mode 2). */
 int atomnas_dwconv_fwd(const void* x, int ldx, long x_ss, const float* in_scale, const float* in_shift, int in_relu, const float* w,
