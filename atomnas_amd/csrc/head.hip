@@ -37,6 +37,9 @@ __global__ __launch_bounds__(256) void k_im2col_stem(const float* __restrict__ i
       for (int e = 0; e < 8; ++e) t[e] = v[8 * g8 + e];
       VecIO<T, 8>::store(o + 8 * g8, t);
     }
+    // a wider pitch (ld is a multiple of 8): whole zero groups up to ld; no iteration at the step's ld = 32
+    const float z8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int c = 32; c < ld; c += 8) VecIO<T, 8>::store(o + c, z8);
   }
 }
 
