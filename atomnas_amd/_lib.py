@@ -64,6 +64,8 @@ SIGNATURES = {
     "atomnas_image_color": [vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp],
     "atomnas_xb_coeffs": [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp],
     "atomnas_fold_jobs": [vp, i32, i32, i64, i64, vp],
+    "atomnas_block_infer": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32,
+                            i32, i32, i32, vp],
 }
 NO_STATUS = {"atomnas_last_error": (ctypes.c_char_p, []), "atomnas_abi_version": (i32, []),
              "atomnas_runtime_version": (i32, []), "atomnas_expand_bwd_supported": (i32, [i32, i32, i32]),
@@ -71,7 +73,9 @@ NO_STATUS = {"atomnas_last_error": (ctypes.c_char_p, []), "atomnas_abi_version":
              "atomnas_project_bwd_dp_supported": (i32, [i64, i32, i32, i32, i32, i64, i32, i64, i32, i32]),
              "atomnas_dwconv_cw_supported": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
              "atomnas_dwconv_mm_supported": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
-             "atomnas_se_pool_parts": (i32, [i32, i32, i32])}
+             "atomnas_se_pool_parts": (i32, [i32, i32, i32]),
+             "atomnas_block_infer_supported": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32]),
+             "atomnas_block_infer_runs": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32])}
 
 ABI_VERSION = 9   # include/atomnas_hip.h ATOMNAS_ABI_VERSION
 _lib = None

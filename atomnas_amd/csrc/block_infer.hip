@@ -1,0 +1,484 @@
+// Inference path: one launch per atomic block (InvertedResidualChannels / InvertedResidualChannelsFused without SE, eval mode)
+//
+//     out = [x +] bn_p( Wp . act(bn_d( dw_k( act(bn_e( We . x )) ) )) )
+//
+// The 6x-wide hidden maps E (expand output) and D (depthwise output) never reach global memory.  A workgroup of 8 waves owns
+// (image, output tile): it stages the x window of the tile (tile + halo of the block's largest k, clipped to the image: the halo
+// outside the image is zeros of the ACTIVATED map, which no expand has to compute) in LDS once, then walks the hidden channels in
+// chunks of CH channels inside one branch segment.  Per chunk:
+//   1. expand on the matrix cores (mfma_f32_16x16x32_bf16, the weight rows as the A operand so that a lane ends up with 4 consecutive
+//      channels of one window pixel), K = inp rounded up to 32;
+//   2. raw value rounded to bf16, bn_e + activation in fp32, fp32 into LDS [window pixel][CH]; window positions outside the image are
+//      zeroed once and never written: EXACT ZERO, not act(shift) (the depthwise convolution pads the activated map);
+//   3. k x k taps from LDS on the VALU in fp32: a lane owns 4 channels x 4 consecutive output pixels of one row;
+//   4. raw value rounded to bf16, bn_d + activation, rounded to bf16 into LDS [tile pixel][CH]: the projection's operand;
+//   5. projection MFMAs into fp32 accumulators [tile pixels x oup] that stay in registers over the whole hidden loop.
+// The epilogue rounds the raw projection sum to bf16, applies bn_p, adds the residual and stores once.  These are the rounding
+// points of the plain bf16 storage model, so a network scores the same through this path and through the training decomposition up
+// to accumulation order.  No atomics; a workgroup depends on its own image only: bit-reproducible and batch invariant.
+//
+// The three BatchNorms arrive as per-channel fp32 scale / shift (atomnas_bn_eval_coeffs), the weights in the pointwise GEMMs' packed
+// layouts (atomnas_pack_weights), the taps tap-major [k*k][channels] per segment.
+#include "common.h"
+
+namespace atomnas {
+namespace {
+
+constexpr int BI_THREADS = 512, BI_WAVES = BI_THREADS / 64, BI_MAXSEG = 8;
+constexpr int BI_R = 4;                                  // output pixels of one row per depthwise work item
+constexpr int BI_B = 8;                                  // 16-byte staging copies in flight per lane
+constexpr size_t BI_LDS_BUDGET = 160 * 1024 - 512;       // gfx950: 160 KiB per CU (the predicate must answer without a device)
+constexpr int BI_MAX_ACC_TILES = 24;                     // 16x16 accumulator tiles per wave: 96 registers of the 256 a lane has at 8 waves
+
+struct BiSeg {
+  const float* taps;   // fp32 [k*k][ldw]
+  int off, ch, k, ldw;
+};
+
+struct BiArgs {
+  const bf16_t* x; bf16_t* out;
+  const bf16_t* we; const bf16_t* wp;
+  const float *es, *eb, *ds, *db, *ps, *pb;
+  int ldx, ldo, ldwe, ldwp;
+  int N, H, W, Ho, Wo, inp, oup, stride, act, expand, res, nseg;
+  BiSeg seg[BI_MAXSEG];
+  // tiling (bi_plan)
+  int toh, tow, tiles_x, ih, iw, ipix, erows, xr16, kp, ch, kmax, tpix, tp16, nt;
+  int xstr, estr, dstr;            // LDS row pitches in elements: x window / weights (bf16), E (fp32), D / projection weights (bf16)
+  unsigned o_xs, o_es, o_ds, o_wes, o_wps, o_ts, o_cs;   // byte offsets of the LDS arrays
+};
+
+struct BiShape {
+  int N, H, W, inp, oup, nseg, off[BI_MAXSEG], ch[BI_MAXSEG], k[BI_MAXSEG], stride, act, expand, res, se, dtype;
+};
+
+struct BiPlan {
+  int toh, tow, ch, mt, ntmax, kmax, kp;
+  size_t lds;
+};
+
+__device__ __forceinline__ float bf16_round(float v) { return (float)(bf16_t)v; }
+
+// K x K taps of 4 channels for BI_R consecutive output pixels of one row.  e: the activated expand map at the strip's first input
+// position (+ the lane's channel quad), t: the chunk's taps at the quad.  Each input value is read once per tap row and feeds every
+// output pixel it belongs to.
+template <int K, int S>
+__device__ __forceinline__ void dw_strip(const float* __restrict__ e, int rowstride, int estr, const float* __restrict__ t, int tstr,
+                                         f32x4 (&acc)[BI_R]) {
+  constexpr int NX = (BI_R - 1) * S + K;
+#pragma unroll 1
+  for (int ky = 0; ky < K; ++ky) {
+    f32x4 tp[K];
+#pragma unroll
+    for (int kx = 0; kx < K; ++kx) tp[kx] = *reinterpret_cast<const f32x4*>(t + (ky * K + kx) * tstr);
+    const float* er = e + ky * rowstride;
+#pragma unroll
+    for (int ix = 0; ix < NX; ++ix) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(er + ix * estr);
+#pragma unroll
+      for (int r = 0; r < BI_R; ++r) {
+        const int kx = ix - r * S;
+        if (kx >= 0 && kx < K) acc[r] += v * tp[kx];
+      }
+    }
+  }
+}
+
+template <int MT, int NTMAX>
+__global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bi_smem[];
+  bf16_t* Xs = reinterpret_cast<bf16_t*>(bi_smem + a.o_xs);     // [xr16][xstr]   x window clipped to the image, zeros beyond inp
+  float* Es = reinterpret_cast<float*>(bi_smem + a.o_es);       // [erows][estr]  activated expand chunk over the whole window
+  bf16_t* Ds = reinterpret_cast<bf16_t*>(bi_smem + a.o_ds);     // [tp16][dstr]   activated depthwise chunk
+  bf16_t* Wes = reinterpret_cast<bf16_t*>(bi_smem + a.o_wes);   // [ch][xstr]     expand weights of the chunk
+  bf16_t* Wps = reinterpret_cast<bf16_t*>(bi_smem + a.o_wps);   // [nt*16][dstr]  projection weights of the chunk
+  float* Ts = reinterpret_cast<float*>(bi_smem + a.o_ts);       // [k*k][ch]      taps of the chunk
+  float* Cs = reinterpret_cast<float*>(bi_smem + a.o_cs);       // [4][ch]        bn_d scale, shift, bn_e scale, shift of the chunk
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int n = blockIdx.y, ty = blockIdx.x / a.tiles_x, tx = blockIdx.x % a.tiles_x;
+  const int oy0 = ty * a.toh, ox0 = tx * a.tow;
+  const int S = a.stride, pmax = (a.kmax - 1) / 2;
+  const int gy0 = oy0 * S - pmax, gx0 = ox0 * S - pmax;   // the window's origin in the input map
+  const int H = a.H, W = a.W, iw = a.iw, ipix = a.ipix;
+  const int xstr = a.xstr, estr = a.estr, dstr = a.dstr, CH = a.ch;
+  const Act act = act_of(a.act);
+  const long img = (long)n * H * W;
+  const bf16x8 zero8 = {};
+  // the window clipped to the image: rows [cy0, cy1) x columns [cx0, cx1) of the input map, cpix pixels in row-major order
+  const int cy0 = max(gy0, 0), cy1 = min(gy0 + a.ih, H), cx0 = max(gx0, 0), cx1 = min(gx0 + iw, W);
+  const int cw = max(cx1 - cx0, 0), cpix = cw * max(cy1 - cy0, 0), cp16 = (cpix + 15) / 16 * 16;
+
+  // Staging copies are 16 bytes per lane and BI_B of them in flight: every copy loop issues its loads first and stores afterwards (one
+  // load round trip per BI_B copies; a workgroup alone on its CU has nothing else to hide the latency of a dependent copy behind).
+  if (a.expand) {
+    const int k8 = a.kp / 8;
+    for (int base = tid; base < cp16 * k8; base += BI_THREADS * BI_B) {
+      bf16x8 v[BI_B];
+#pragma unroll
+      for (int j = 0; j < BI_B; ++j) {
+        const int u = base + j * BI_THREADS, p = u / k8, c = (u % k8) * 8;
+        v[j] = zero8;
+        if (p < cpix && c < a.inp) v[j] = *reinterpret_cast<const bf16x8*>(a.x + (img + (long)(cy0 + p / cw) * W + cx0 + p % cw) * a.ldx + c);
+      }
+#pragma unroll
+      for (int j = 0; j < BI_B; ++j) {
+        const int u = base + j * BI_THREADS, p = u / k8, c = (u % k8) * 8;
+        if (p < cp16) *reinterpret_cast<bf16x8*>(Xs + p * xstr + c) = v[j];
+      }
+    }
+    for (int u = tid; u < a.erows * (estr / 4); u += BI_THREADS) *reinterpret_cast<f32x4*>(Es + u * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int u = tid; u < a.tp16 * (dstr / 8); u += BI_THREADS) *reinterpret_cast<bf16x8*>(Ds + u * 8) = zero8;
+
+  f32x4 acc[MT][NTMAX];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int t = 0; t < NTMAX; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int si = 0; si < a.nseg; ++si) {
+    const BiSeg sg = a.seg[si];
+    const int K = sg.k, off = pmax - (K - 1) / 2;   // the segment's own padding inside the window of the largest k
+    for (int c0 = sg.off; c0 < sg.off + sg.ch; c0 += CH) {
+      const int cv = min(CH, sg.off + sg.ch - c0);   // channels of this chunk (a multiple of 8; of 16 in an expanding block)
+      const int cv32 = (cv + 31) / 32 * 32;
+      // ---- stage the chunk's expand weights, projection weights, taps and BatchNorm coefficients: ONE index space of 16-byte copies, so
+      // that the chunk pays one load round trip (a coefficient load from global memory inside a phase stalls the whole workgroup)
+      {
+        const int k8 = a.kp / 8, c8 = cv32 / 8, c4 = cv / 4;
+        const int nwe = a.expand ? cv * k8 : 0, nwp = a.nt * 16 * c8, nts = K * K * c4, total = nwe + nwp + nts + (a.expand ? 4 : 2) * c4;
+        for (int base = tid; base < total; base += BI_THREADS * BI_B) {
+          f32x4 v[BI_B];
+          unsigned dst[BI_B];   // byte offset in LDS; ~0u: nothing to store
+#pragma unroll
+          for (int j = 0; j < BI_B; ++j) {
+            int u = base + j * BI_THREADS;
+            v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            dst[j] = ~0u;
+            if (u < nwe) {
+              const int r = u / k8, c = (u % k8) * 8;
+              v[j] = *reinterpret_cast<const f32x4*>(a.we + (long)(c0 + r) * a.ldwe + c);
+              dst[j] = a.o_wes + (unsigned)(r * xstr + c) * 2;
+            } else if (u < nwe + nwp) {
+              u -= nwe;
+              const int o = u / c8, c = (u % c8) * 8;
+              if (c < cv) v[j] = *reinterpret_cast<const f32x4*>(a.wp + (long)o * a.ldwp + c0 + c);
+              dst[j] = a.o_wps + (unsigned)(o * dstr + c) * 2;
+            } else if (u < nwe + nwp + nts) {
+              u -= nwe + nwp;
+              const int t = u / c4, c = (u % c4) * 4;
+              v[j] = *reinterpret_cast<const f32x4*>(sg.taps + (long)t * sg.ldw + (c0 - sg.off) + c);
+              dst[j] = a.o_ts + (unsigned)(t * CH + c) * 4;
+            } else if (u < total) {
+              u -= nwe + nwp + nts;
+              const int w = u / c4, c = (u % c4) * 4;
+              const float* src = w == 0 ? a.ds : w == 1 ? a.db : w == 2 ? a.es : a.eb;
+              v[j] = *reinterpret_cast<const f32x4*>(src + c0 + c);
+              dst[j] = a.o_cs + (unsigned)(w * CH + c) * 4;
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < BI_B; ++j)
+            if (dst[j] != ~0u) *reinterpret_cast<f32x4*>(bi_smem + dst[j]) = v[j];
+        }
+      }
+      __syncthreads();
+      // ---- E chunk: expand MFMAs + bn_e + activation over the pixels inside the image
+      if (a.expand) {
+        const int ntile = cv / 16, ksteps = a.kp / 32;
+        for (int mt = wave; mt < cp16 / 16; mt += BI_WAVES) {
+          const int p = mt * 16 + l15;
+          const bool inside = p < cpix;
+          const int wp = inside ? (cy0 + p / cw - gy0) * iw + (cx0 + p % cw - gx0) : 0;   // the pixel's place in the window
+          const bf16_t* xb = Xs + p * xstr + 8 * lq;
+          for (int t0 = 0; t0 < ntile; t0 += 2) {
+            const bool two = t0 + 1 < ntile;
+            f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
+            const bf16_t* w0 = Wes + (t0 * 16 + l15) * xstr + 8 * lq;
+            const bf16_t* w1 = w0 + (two ? 16 * xstr : 0);
+            for (int ks = 0; ks < ksteps; ++ks) {
+              const bf16x8 b = *reinterpret_cast<const bf16x8*>(xb + ks * 32);
+              e0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(w0 + ks * 32), b, e0, 0, 0, 0);
+              e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(w1 + ks * 32), b, e1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              if (h == 1 && !two) break;
+              const f32x4 e = h ? e1 : e0;
+              const int c = (t0 + h) * 16 + lq * 4;
+              const f32x4 sc = *reinterpret_cast<const f32x4*>(Cs + 2 * CH + c), sh = *reinterpret_cast<const f32x4*>(Cs + 3 * CH + c);
+              float v[4];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) v[r] = bf16_round(e[r]) * sc[r] + sh[r];
+              act_apply_v(v, act);
+              if (inside) *reinterpret_cast<f32x4*>(Es + wp * estr + c) = f32x4{v[0], v[1], v[2], v[3]};
+            }
+          }
+        }
+      } else {   // the first block of a network: the depthwise stage reads x itself
+        const int c8 = cv / 8;
+        for (int base = tid; base < ipix * c8; base += BI_THREADS * BI_B) {
+          bf16x8 v[BI_B];
+#pragma unroll
+          for (int j = 0; j < BI_B; ++j) {
+            const int u = base + j * BI_THREADS, p = u / c8, c = (u % c8) * 8;
+            const int gy = gy0 + p / iw, gx = gx0 + p % iw;
+            v[j] = zero8;
+            if (p < ipix && gy >= 0 && gy < H && gx >= 0 && gx < W) v[j] = *reinterpret_cast<const bf16x8*>(a.x + (img + (long)gy * W + gx) * a.ldx + c0 + c);
+          }
+#pragma unroll
+          for (int j = 0; j < BI_B; ++j) {
+            const int u = base + j * BI_THREADS, p = u / c8, c = (u % c8) * 8;
+            if (p < ipix) {
+              *reinterpret_cast<f32x4*>(Es + p * estr + c) = f32x4{(float)v[j][0], (float)v[j][1], (float)v[j][2], (float)v[j][3]};
+              *reinterpret_cast<f32x4*>(Es + p * estr + c + 4) = f32x4{(float)v[j][4], (float)v[j][5], (float)v[j][6], (float)v[j][7]};
+            }
+          }
+        }
+      }
+      __syncthreads();
+      // ---- D chunk: taps on the VALU + bn_d + activation -> bf16 operand
+      {
+        const int nq = cv32 / 4, strips = (a.tow + BI_R - 1) / BI_R;
+        for (int it = tid; it < nq * strips * a.toh; it += BI_THREADS) {
+          const int q = it % nq, rest = it / nq;
+          const int ox = (rest % strips) * BI_R, oy = rest / strips;
+          f32x4 d[BI_R];
+#pragma unroll
+          for (int r = 0; r < BI_R; ++r) d[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (q * 4 < cv) {   // (else: the zero columns that fill the projection's last k-step)
+            const float* e = Es + ((oy * S + off) * iw + ox * S + off) * estr + q * 4;
+            const float* t = Ts + q * 4;
+            const int rs = iw * estr;
+            switch (K * 2 + S) {
+              case 3 * 2 + 1: dw_strip<3, 1>(e, rs, estr, t, CH, d); break;
+              case 3 * 2 + 2: dw_strip<3, 2>(e, rs, estr, t, CH, d); break;
+              case 5 * 2 + 1: dw_strip<5, 1>(e, rs, estr, t, CH, d); break;
+              case 5 * 2 + 2: dw_strip<5, 2>(e, rs, estr, t, CH, d); break;
+              case 7 * 2 + 1: dw_strip<7, 1>(e, rs, estr, t, CH, d); break;
+              case 7 * 2 + 2: dw_strip<7, 2>(e, rs, estr, t, CH, d); break;
+              case 9 * 2 + 1: dw_strip<9, 1>(e, rs, estr, t, CH, d); break;
+              case 9 * 2 + 2: dw_strip<9, 2>(e, rs, estr, t, CH, d); break;
+              case 11 * 2 + 1: dw_strip<11, 1>(e, rs, estr, t, CH, d); break;
+              default: dw_strip<11, 2>(e, rs, estr, t, CH, d); break;
+            }
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(Cs + q * 4), sh = *reinterpret_cast<const f32x4*>(Cs + CH + q * 4);
+#pragma unroll
+            for (int r = 0; r < BI_R; ++r) {
+              float v[4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) v[j] = bf16_round(d[r][j]) * sc[j] + sh[j];
+              act_apply_v(v, act);
+              d[r] = f32x4{v[0], v[1], v[2], v[3]};
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < BI_R; ++r)
+            if (ox + r < a.tow) {
+              const float v[4] = {d[r][0], d[r][1], d[r][2], d[r][3]};
+              VecIO<bf16_t, 4>::store(Ds + (oy * a.tow + ox + r) * dstr + q * 4, v);
+            }
+        }
+      }
+      __syncthreads();
+      // ---- projection: accumulate the chunk
+      for (int ks = 0; ks < cv32 / 32; ++ks) {
+        bf16x8 b[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          const int mt = min(wave + BI_WAVES * m, a.tp16 / 16 - 1);
+          b[m] = *reinterpret_cast<const bf16x8*>(Ds + (mt * 16 + l15) * dstr + ks * 32 + 8 * lq);
+        }
+#pragma unroll
+        for (int t = 0; t < NTMAX; ++t) {
+          if (t < a.nt) {
+            const bf16x8 w = *reinterpret_cast<const bf16x8*>(Wps + (t * 16 + l15) * dstr + ks * 32 + 8 * lq);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, b[m], acc[m][t], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue: raw sum rounded to bf16, bn_p, residual, one store
+  const long oimg = (long)n * a.Ho * a.Wo;
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int mt = wave + BI_WAVES * m;
+    const int p = mt * 16 + l15;
+    const int oy = oy0 + p / a.tow, ox = ox0 + p % a.tow;
+    if (mt * 16 >= a.tp16 || p >= a.tpix || oy >= a.Ho || ox >= a.Wo) continue;
+#pragma unroll
+    for (int t = 0; t < NTMAX; ++t) {
+      const int o = t * 16 + lq * 4;
+      if (t < a.nt && o < a.oup) {
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(a.ps + o), sh = *reinterpret_cast<const f32x4*>(a.pb + o);
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = bf16_round(acc[m][t][r]) * sc[r] + sh[r];
+        if (a.res) {
+          float xr[4];
+          VecIO<bf16_t, 4>::load(a.x + (img + (long)oy * W + ox) * a.ldx + o, xr);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += xr[r];
+        }
+        VecIO<bf16_t, 4>::store(a.out + (oimg + (long)oy * a.Wo + ox) * a.ldo + o, v);
+      }
+    }
+  }
+}
+
+inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+
+// The COMPLETE accept / reject decision and the tiling, pure host arithmetic (no device query): the entry point and the predicate share it.
+bool bi_plan(const BiShape& s, BiPlan& p) {
+  if (s.dtype != DT_BF16 || s.se) return false;
+  if (s.N < 1 || s.N > 65535 || s.H < 1 || s.W < 1 || (long)s.H * s.W > (1L << 24)) return false;
+  if (s.stride != 1 && s.stride != 2) return false;
+  if (s.act < ACT_NONE || s.act > ACT_SWISH) return false;
+  if (s.nseg < 1 || s.nseg > BI_MAXSEG) return false;
+  if (s.inp < 8 || s.inp % 8 || s.inp > 1024 || s.oup < 8 || s.oup % 8 || s.oup > 320) return false;
+  if (s.res && (s.stride != 1 || s.inp != s.oup)) return false;
+  int kmax = 0, chmax = 0, end = 0;
+  for (int i = 0; i < s.nseg; ++i) {
+    const int k = s.k[i];
+    if (k != 3 && k != 5 && k != 7 && k != 9 && k != 11) return false;
+    if (s.ch[i] < 8 || s.ch[i] % (s.expand ? 16 : 8) || s.off[i] < end || s.off[i] % 8) return false;
+    end = s.off[i] + s.ch[i];
+    kmax = k > kmax ? k : kmax;
+    chmax = s.ch[i] > chmax ? s.ch[i] : chmax;
+  }
+  if (end > 8192 || (!s.expand && end > s.inp)) return false;
+  const int nt = (s.oup + 15) / 16;
+  const int ntmax = nt <= 2 ? 2 : nt <= 4 ? 4 : nt <= 8 ? 8 : nt <= 12 ? 12 : 20;
+  const int Ho = (s.H - 1) / s.stride + 1, Wo = (s.W - 1) / s.stride + 1;
+  const int kp = s.expand ? pad_to(s.inp, 32) : 0;
+  // tiles: a whole map of up to 16 MFMA row tiles per workgroup (no expand recompute), else from the largest tile down
+  const int cand[6][2] = {{Ho, Wo}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}};
+  for (int ci = 0; ci < 6; ++ci) {
+    if (ci == 0 && (long)Ho * Wo > 256) continue;
+    const int toh = cand[ci][0] < Ho ? cand[ci][0] : Ho, tow = cand[ci][1] < Wo ? cand[ci][1] : Wo;
+    const int tp16 = pad_to(toh * tow, 16), mt = (tp16 / 16 + BI_WAVES - 1) / BI_WAVES;
+    if (mt > 2 || mt * ntmax > BI_MAX_ACC_TILES) continue;
+    const int ih = (toh - 1) * s.stride + kmax, iw = (tow - 1) * s.stride + kmax, ipix = ih * iw;
+    const int xr16 = pad_to((ih < s.H ? ih : s.H) * (iw < s.W ? iw : s.W), 16);   // the window clipped to the image
+    const int erows = ipix + 8;   // slack: the last strip of a row reads up to 3 * stride pixels past it
+    for (int ch = pad_to(chmax, 32) < 128 ? pad_to(chmax, 32) : 128; ch >= 32; ch -= 32) {
+      const size_t lds = (s.expand ? (size_t)(xr16 + ch) * (kp + 8) * 2 : 0) + (size_t)erows * (ch + 4) * 4 + (size_t)(tp16 + nt * 16) * (ch + 8) * 2 +
+                         (size_t)(kmax * kmax + 4) * ch * 4;
+      if (lds <= BI_LDS_BUDGET) {
+        p.toh = toh, p.tow = tow, p.ch = ch, p.mt = mt, p.ntmax = ntmax, p.kmax = kmax, p.kp = kp, p.lds = lds;
+        return true;
+      }
+    }
+  }
+  return false;
+}
+
+// Where the kernel is FASTER than the launch-per-stage decomposition (functional.block_forward in eval mode), measured block by block
+// on an MI355X at batch 256 (profiles/infer_bench.txt; the table is in DESIGN.md): expanding blocks whose whole map sits in one
+// workgroup (stride 1, no expand recompute) with little hidden work -- padded hidden channels x window pixels <= 140,000, the searched
+// networks' 14x14 and 7x7 stages -- and an output of at most 192 channels.  Everything else measured slower (the chunk loop of one
+// workgroup per CU does not hide its phases behind each other) and is reported as unsupported, so that it takes the existing path.
+bool bi_profitable(const BiShape& s, const BiPlan& p) {
+  const int Ho = (s.H - 1) / s.stride + 1, Wo = (s.W - 1) / s.stride + 1;
+  if (!s.expand || s.stride != 1 || p.toh != Ho || p.tow != Wo || s.oup > 192) return false;
+  long hidden = 0;
+  for (int i = 0; i < s.nseg; ++i) hidden += s.ch[i];
+  const long ipix = (long)((p.toh - 1) * s.stride + p.kmax) * ((p.tow - 1) * s.stride + p.kmax);
+  return hidden * ipix <= 140000;
+}
+
+template <int MT, int NTMAX>
+int bi_run(const BiArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  (void)resident_per_cu(k_block_infer<MT, NTMAX>, BI_THREADS, lds);   // opts the kernel into its dynamic LDS size (cached)
+  hipLaunchKernelGGL((k_block_infer<MT, NTMAX>), grid, dim3(BI_THREADS), lds, st, a);
+  return check_launch("block_infer");
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+}  // namespace atomnas
+
+using namespace atomnas;
+
+static void bi_shape(BiShape& s, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
+                     int stride, int act, int expand, int residual, int se, int dtype) {
+  s.N = N, s.H = H, s.W = W, s.inp = inp, s.oup = oup, s.nseg = nseg, s.stride = stride, s.act = act, s.expand = expand != 0,
+  s.res = residual != 0, s.se = se != 0, s.dtype = dtype;
+  for (int i = 0; i < nseg && i < BI_MAXSEG; ++i) s.off[i] = seg_off[i], s.ch[i] = seg_ch[i], s.k[i] = seg_k[i];
+}
+
+extern "C" int atomnas_block_infer_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                        const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  BiShape s;
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype);
+  BiPlan p;
+  return bi_plan(s, p) ? 1 : 0;
+}
+
+extern "C" int atomnas_block_infer_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                             const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  BiShape s;
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype);
+  BiPlan p;
+  return bi_plan(s, p) && bi_profitable(s, p) ? 1 : 0;
+}
+
+extern "C" int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
+                                   const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale,
+                                   const float* d_shift, const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup,
+                                   int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
+                                   int residual, int dtype, void* stream) {
+  ATOMNAS_REQUIRE(nseg >= 1 && nseg <= BI_MAXSEG && seg_off && seg_ch && seg_k && taps, "block_infer: 1..%d segments with offsets, channels, kernel sizes and taps", BI_MAXSEG);
+  BiShape s;
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
+  BiPlan p;
+  ATOMNAS_REQUIRE(bi_plan(s, p), "block_infer: shape outside the fused kernel's envelope (ask atomnas_block_infer_runs first): N=%d %dx%d inp=%d oup=%d stride=%d dtype=%d",
+                  N, H, W, inp, oup, stride, dtype);
+  ATOMNAS_REQUIRE(p.lds <= max_lds_bytes(), "block_infer: needs %zu bytes of LDS, the device grants %zu", p.lds, max_lds_bytes());
+  ATOMNAS_REQUIRE(x && out && wp && d_scale && d_shift && p_scale && p_shift && (!s.expand || (we && e_scale && e_shift)), "block_infer: null operand");
+  ATOMNAS_REQUIRE(ldx >= inp && ldx % 8 == 0 && ldo >= oup && ldo % 4 == 0 && aligned16(x) && ((uintptr_t)out & 7) == 0, "block_infer: activation pitch / alignment");
+  const int hid = seg_off[nseg - 1] + seg_ch[nseg - 1];
+  ATOMNAS_REQUIRE(ldwp >= hid && ldwp % 8 == 0 && aligned16(wp) && (!s.expand || (ldwe >= p.kp && ldwe % 8 == 0 && aligned16(we))), "block_infer: packed weight pitch / alignment");
+  ATOMNAS_REQUIRE(aligned16(d_scale) && aligned16(d_shift) && aligned16(p_scale) && aligned16(p_shift) && aligned16(e_scale) && aligned16(e_shift), "block_infer: coefficient vectors must be 16-byte aligned");
+  BiArgs a = {};
+  a.x = (const bf16_t*)x, a.out = (bf16_t*)out, a.we = (const bf16_t*)we, a.wp = (const bf16_t*)wp;
+  a.es = e_scale, a.eb = e_shift, a.ds = d_scale, a.db = d_shift, a.ps = p_scale, a.pb = p_shift;
+  a.ldx = ldx, a.ldo = ldo, a.ldwe = ldwe, a.ldwp = ldwp;
+  a.N = N, a.H = H, a.W = W, a.Ho = (H - 1) / stride + 1, a.Wo = (W - 1) / stride + 1, a.inp = inp, a.oup = oup, a.stride = stride, a.act = act,
+  a.expand = s.expand, a.res = s.res, a.nseg = nseg;
+  for (int i = 0; i < nseg; ++i) {
+    ATOMNAS_REQUIRE(taps[i] && aligned16(taps[i]), "block_infer: taps of segment %d missing or not 16-byte aligned", i);
+    a.seg[i] = BiSeg{taps[i], seg_off[i], seg_ch[i], seg_k[i], seg_ch[i]};
+  }
+  a.toh = p.toh, a.tow = p.tow, a.kmax = p.kmax, a.kp = p.kp, a.ch = p.ch;
+  a.tiles_x = (a.Wo + p.tow - 1) / p.tow;
+  const int tiles_y = (a.Ho + p.toh - 1) / p.toh;
+  a.ih = (p.toh - 1) * stride + p.kmax, a.iw = (p.tow - 1) * stride + p.kmax, a.ipix = a.ih * a.iw, a.erows = a.ipix + 8;
+  a.xr16 = pad_to((a.ih < H ? a.ih : H) * (a.iw < W ? a.iw : W), 16);
+  a.tpix = p.toh * p.tow, a.tp16 = pad_to(a.tpix, 16), a.nt = (oup + 15) / 16;
+  a.xstr = p.kp + 8, a.estr = p.ch + 4, a.dstr = p.ch + 8;
+  size_t o = 0;
+  a.o_xs = (unsigned)o, o += s.expand ? (size_t)a.xr16 * a.xstr * 2 : 0;
+  a.o_wes = (unsigned)o, o += s.expand ? (size_t)p.ch * a.xstr * 2 : 0;
+  a.o_es = (unsigned)o, o += (size_t)a.erows * a.estr * 4;
+  a.o_ds = (unsigned)o, o += (size_t)a.tp16 * a.dstr * 2;
+  a.o_wps = (unsigned)o, o += (size_t)a.nt * 16 * a.dstr * 2;
+  a.o_ts = (unsigned)o, o += (size_t)p.kmax * p.kmax * p.ch * 4;
+  a.o_cs = (unsigned)o, o += (size_t)4 * p.ch * 4;
+  ATOMNAS_REQUIRE(o == p.lds, "block_infer: LDS layout (%zu) and plan (%zu) disagree", o, p.lds);
+  const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)N);
+  hipStream_t st = (hipStream_t)stream;
+#define X(MT, NT) if (p.mt == MT && p.ntmax == NT) return bi_run<MT, NT>(a, grid, p.lds, st);
+  X(1, 2) X(1, 4) X(1, 8) X(1, 12) X(1, 20) X(2, 2) X(2, 4) X(2, 8) X(2, 12)
+#undef X
+  ATOMNAS_REQUIRE(false, "block_infer: no instance for %d x %d accumulator tiles", p.mt, p.ntmax);
+}

@@ -387,6 +387,36 @@ def bn_apply(x, scale, shift, relu, res, y, M, C):
          _ld(y), M, C, dt_code(x.dtype), _stream())
 
 
+def _ints(v):
+    return (ctypes.c_int * len(v))(*[int(i) for i in v])
+
+
+def block_infer_supported(N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype, profitable=True):
+    """whether atomnas_block_infer serves this block (a host predicate: no GPU needed) -- and, with profitable, measured faster than the
+    existing path for shapes of its kind (atomnas_block_infer_supported; without: atomnas_block_infer_runs).  seg_*: per branch segment
+    its first hidden channel, its padded channel count and its kernel size; dtype: a torch dtype or the C ABI's code"""
+    n = len(seg_off)
+    if n == 0 or len(seg_ch) != n or len(seg_k) != n:
+        return False
+    fn = _lib.load().atomnas_block_infer_supported if profitable else _lib.load().atomnas_block_infer_runs
+    return bool(fn(int(N), int(H), int(W), int(inp), int(oup), n, _ints(seg_off), _ints(seg_ch),
+                                                          _ints(seg_k), int(stride), int(act), int(bool(expand)), int(bool(residual)),
+                                                          int(bool(se)), dtype if isinstance(dtype, int) else dt_code(dtype)))
+
+
+def block_infer(x, out, we_pack, wp_pack, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, seg_off, seg_ch,
+                seg_k, stride, act, expand, residual):
+    """One launch for a whole atomic block in eval mode (include/atomnas_hip.h, csrc/block_infer.hip): x [N*H*W, ld] -> out [N*Ho*Wo, ld],
+    bf16; the BatchNorms as folded scale / shift vectors over the padded hidden layout; taps: one fp32 [k*k][seg_ch] tensor per segment"""
+    _chk_cuda(x, out, wp_pack, *taps)
+    n = len(seg_off)
+    tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in taps])
+    call("atomnas_block_infer", _p(x), _ld(x), _p(out), _ld(out), _p(we_pack), we_pack.stride(0) if we_pack is not None else 0, _p(wp_pack),
+         wp_pack.stride(0), tp, _p(e_scale), _p(e_shift), _p(d_scale), _p(d_shift), _p(p_scale), _p(p_shift), int(N), int(H), int(W), int(inp),
+         int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act), int(bool(expand)), int(bool(residual)),
+         dt_code(x.dtype), _stream())
+
+
 def bnbwd_apply(g, x, c1, c2, c3, y, M, C):
     """y = c1*g + c2*x + c3 (plain [M, C] tensors): the differentiated BatchNorm output, materialised once"""
     _chk_cuda(g, x, y)

@@ -394,6 +394,33 @@ typedef struct atomnas_gather_job {
 } atomnas_gather_job;
 int atomnas_gather_jobs(const void* jobs_dev, int njobs, long nblocks, void* stream);
 
+/* ---- inference: a whole atomic block (models/mobilenet_base.py InvertedResidualChannels / InvertedResidualChannelsFused without SE)
+ *      in eval mode as ONE launch (csrc/block_infer.hip; additive in ABI 9):
+ *        out = [x +] bn_p( Wp . act(bn_d( dw_k( act(bn_e( We . x )) ) )) )
+ *   The hidden maps stay on chip.  bf16 storage only; rounding points of the plain bf16 storage model (raw expand, depthwise and
+ *   projection outputs rounded to bf16 before their BatchNorm; activated expand output and taps fp32; activated depthwise output
+ *   rounded to bf16), zero padding applied to the ACTIVATED expand output.  No atomics; image i's output depends on image i alone.
+ *   x [N*H*W][ldx], out [N*Ho*Wo][ldo] (Ho = (H-1)/stride + 1, padding (k-1)/2): plain layouts, ldx % 8 == 0, ldo % 4 == 0.
+ *   Hidden channels: nseg <= 8 branch segments {seg_off, seg_ch, seg_k} (host arrays), ascending, seg_off % 8 == 0, seg_ch the PADDED
+ *   width (a multiple of 16; of 8 when expand == 0), seg_k in {3,5,7,9,11}.  taps: host array of nseg device pointers to fp32
+ *   [k*k][seg_ch] (atomnas_pack_weights mode 2).  we: [hidden][ldwe >= inp rounded up to 32], wp: [oup rounded up to 16][ldwp >= hidden],
+ *   both atomnas_pack_weights mode 0 with zeroed padding.  *_scale / *_shift: fp32 per-channel BatchNorm coefficients
+ *   (atomnas_bn_eval_coeffs) over the hidden layout (e, d: zeros at padding channels) and over oup (p), 16-byte aligned.
+ *   expand == 0 (first block): the depthwise stage reads channels seg_off.. of x itself; we / e_scale / e_shift may be NULL.
+ *   residual != 0: stride 1 and inp == oup.  act: 0 none, 1 ReLU, 2 ReLU6, 3 Swish.
+ * atomnas_block_infer_runs: pure host predicate (no device needed), 1 when atomnas_block_infer can run the shape: bf16, no SE,
+ *   stride 1 / 2, inp / oup multiples of 8, oup <= 320, and a tile + hidden-channel chunk that fits 160 KiB of LDS.
+ * atomnas_block_infer_supported: the same AND the kernel measured faster than the launch-per-stage decomposition for shapes of this
+ *   kind (csrc/block_infer.hip bi_profitable; DESIGN.md lists the measurements): what a caller asks before it leaves the existing path. */
+int atomnas_block_infer_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
+                             int stride, int act, int expand, int residual, int se, int dtype);
+int atomnas_block_infer_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
+                                  int stride, int act, int expand, int residual, int se, int dtype);
+int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
+                        const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale, const float* d_shift,
+                        const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off,
+                        const int* seg_ch, const int* seg_k, int stride, int act, int expand, int residual, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

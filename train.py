@@ -113,6 +113,16 @@ def calibrate_bn(model, epoch):
         udist.allreduce_bn(model)
 
 
+def eval_net(model):
+    """What an evaluation pass calls: the model itself, or with `fused_inference` its compilation for inference (atomnas_amd/inference.py:
+    one fused launch per atomic block).  Compiled AFTER the BatchNorm calibration, which needs batch statistics and stays on the
+    model's own path; the compiled network folds the calibrated statistics into constants."""
+    if not cfg.FLAGS.get('fused_inference', False):
+        return model
+    from atomnas_amd.inference import compile_for_inference
+    return compile_for_inference(model)
+
+
 def validate(epoch, model_wrapper, ema, criterion, meters, steps):
     """EMA model -> BN calibration (cumulative statistics) -> evaluation (train.py:419-458), on synthetic batches."""
     import common as mc
@@ -122,11 +132,12 @@ def validate(epoch, model_wrapper, ema, criterion, meters, steps):
     if FLAGS.get('bn_calibration', False):
         calibrate_bn(model, epoch)
     model.eval()
+    net = eval_net(model)
     with torch.no_grad():
         val = (device_batches(LOADERS[2], steps) if LOADERS is not None and LOADERS[2] is not None else
                fake_batches(FLAGS.per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'], steps, 11))
         for x, y in val:
-            mc.forward_loss(model, criterion, x, y, meters)
+            mc.forward_loss(net, criterion, x, y, meters)
     return meters.flush(), eval_wrapper
 
 
@@ -175,10 +186,11 @@ def evaluate(model_wrapper, ema, epoch=0, phase='test'):
     criterion = optim.CrossEntropyLabelSmooth(FLAGS.model_kwparams['num_classes'], 0.0, reduction='none')
     meters = mc.get_meters(phase)
     model.eval()
+    net = eval_net(model)
     seen = 0
     with torch.no_grad():
         for x, y in device_batches(LOADERS[3], None):
-            mc.forward_loss(model, criterion, x, y, meters)
+            mc.forward_loss(net, criterion, x, y, meters)
             seen += x.shape[0]
     if FLAGS.use_distributed:
         n = torch.tensor([seen], dtype=torch.float64, device='cuda')
