@@ -66,6 +66,8 @@ SIGNATURES = {
     "atomnas_fold_jobs": [vp, i32, i32, i64, i64, vp],
     "atomnas_block_infer": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32,
                             i32, i32, i32, vp],
+    "atomnas_block_infer_se": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32,
+                               i32, i32, i32, vp, vp, vp, vp, i32, i32, vp],
 }
 NO_STATUS = {"atomnas_last_error": (ctypes.c_char_p, []), "atomnas_abi_version": (i32, []),
              "atomnas_runtime_version": (i32, []), "atomnas_expand_bwd_supported": (i32, [i32, i32, i32]),
@@ -75,7 +77,9 @@ NO_STATUS = {"atomnas_last_error": (ctypes.c_char_p, []), "atomnas_abi_version":
              "atomnas_dwconv_mm_supported": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
              "atomnas_se_pool_parts": (i32, [i32, i32, i32]),
              "atomnas_block_infer_supported": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32]),
-             "atomnas_block_infer_runs": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32])}
+             "atomnas_block_infer_runs": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32]),
+             "atomnas_block_infer_se_supported": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32]),
+             "atomnas_block_infer_se_runs": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32])}
 
 ABI_VERSION = 9   # include/atomnas_hip.h ATOMNAS_ABI_VERSION
 _lib = None

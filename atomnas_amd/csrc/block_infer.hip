@@ -1,4 +1,4 @@
-// Inference path: one launch per atomic block (InvertedResidualChannels / InvertedResidualChannelsFused without SE, eval mode)
+// Inference path: one launch per atomic block (InvertedResidualChannels / InvertedResidualChannelsFused, eval mode; with SE: below)
 //
 //     out = [x +] bn_p( Wp . act(bn_d( dw_k( act(bn_e( We . x )) ) )) )
 //
@@ -16,6 +16,18 @@
 // The epilogue rounds the raw projection sum to bf16, applies bn_p, adds the residual and stores once.  These are the rounding
 // points of the plain bf16 storage model, so a network scores the same through this path and through the training decomposition up
 // to accumulation order.  No atomics; a workgroup depends on its own image only: bit-reproducible and batch invariant.
+//
+// Squeeze-and-Excitation (InvertedResidualChannelsFused with se_ratio, the "+" networks; template parameter SE, atomnas_block_infer_se):
+//     A = act(bn_d(bf16(dw)))  fp32, not rounded;   s[c] = mean_hw A[:, c];   gate = sigmoid(W2 . act(W1 . s + b1) + b2);   out = [x +] bn_p(bf16(Wp . bf16(gate * A)))
+// The gate of one channel needs the squeeze of ALL hidden channels, so the kernel serves SE only where ONE workgroup owns the whole map
+// (stride 1, at most 256 pixels) and runs the chunk loop TWICE (the same code, so the recomputed A is bit-identical):
+//   pass 0  steps 1-3, bn_d + activation in fp32; every depthwise work item adds its own 4 pixels and writes one fp32 partial per
+//           (row, strip) into the Ds / Wps region (idle in this pass); after the barrier one thread per channel adds the partials in
+//           row-major order into pooled[HT].  Only tile pixels are ever summed: the padding rows of the MFMA tiles do not exist here.
+//   gate    hpre: a wave per hidden unit, butterfly sum over the channels; gate: a thread per channel, the hidden units in sequence
+//           (the scheme and the packed fp32 operands of csrc/se.hip k_se_mlp).  pooled, gate and act(hpre) live in LDS.
+//   pass 1  steps 1-5 with bf16(gate * A) as the projection's operand.
+// The expand and tap work is done twice (recompute factor 2); every sum has a fixed order that depends on the shape alone.
 //
 // The three BatchNorms arrive as per-channel fp32 scale / shift (atomnas_bn_eval_coeffs), the weights in the pointwise GEMMs' packed
 // layouts (atomnas_pack_weights), the taps tap-major [k*k][channels] per segment.
@@ -48,8 +60,18 @@ struct BiArgs {
   unsigned o_xs, o_es, o_ds, o_wes, o_wps, o_ts, o_cs;   // byte offsets of the LDS arrays
 };
 
+// the SE instances' arguments: BiArgs (so that the plain instances keep theirs, and their code) + the gate's operands
+struct BiArgsSe : BiArgs {
+  const float *w1p, *w2t, *b1, *b2p;   // fp32 [se_hid][ldse] x 2 (channels contiguous, zeros in padding columns), [se_hid], [HT]
+  int se_hid, ldse, ht;
+  float inv_hw;
+  unsigned o_pool, o_gate, o_hs;       // byte offsets of pooled[HT], gate[HT], act(hpre)[se_hid]
+};
+template <bool SE> struct BiArgsOf { typedef BiArgs type; };
+template <> struct BiArgsOf<true> { typedef BiArgsSe type; };
+
 struct BiShape {
-  int N, H, W, inp, oup, nseg, off[BI_MAXSEG], ch[BI_MAXSEG], k[BI_MAXSEG], stride, act, expand, res, se, dtype;
+  int N, H, W, inp, oup, nseg, off[BI_MAXSEG], ch[BI_MAXSEG], k[BI_MAXSEG], stride, act, expand, res, se, dtype, se_hid;
 };
 
 struct BiPlan {
@@ -84,8 +106,8 @@ __device__ __forceinline__ void dw_strip(const float* __restrict__ e, int rowstr
   }
 }
 
-template <int MT, int NTMAX>
-__global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
+template <int MT, int NTMAX, bool SE>
+__global__ __launch_bounds__(BI_THREADS) void k_block_infer(const typename BiArgsOf<SE>::type a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bi_smem[];
   bf16_t* Xs = reinterpret_cast<bf16_t*>(bi_smem + a.o_xs);     // [xr16][xstr]   x window clipped to the image, zeros beyond inp
   float* Es = reinterpret_cast<float*>(bi_smem + a.o_es);       // [erows][estr]  activated expand chunk over the whole window
@@ -131,6 +153,8 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
     for (int u = tid; u < a.erows * (estr / 4); u += BI_THREADS) *reinterpret_cast<f32x4*>(Es + u * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int u = tid; u < a.tp16 * (dstr / 8); u += BI_THREADS) *reinterpret_cast<bf16x8*>(Ds + u * 8) = zero8;
+  if constexpr (SE)   // channels between two segments belong to no chunk: their squeeze is zero (and their gate columns hold zeros)
+    for (int c = tid; c < a.ht; c += BI_THREADS) reinterpret_cast<float*>(bi_smem + a.o_pool)[c] = 0.f;
 
   f32x4 acc[MT][NTMAX];
 #pragma unroll
@@ -138,6 +162,8 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
 #pragma unroll
     for (int t = 0; t < NTMAX; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  int pass = 0;   // SE: the chunk loop runs twice, 0 squeeze, 1 project
+  do {
   for (int si = 0; si < a.nseg; ++si) {
     const BiSeg sg = a.seg[si];
     const int K = sg.k, off = pmax - (K - 1) / 2;   // the segment's own padding inside the window of the largest k
@@ -148,7 +174,7 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
       // that the chunk pays one load round trip (a coefficient load from global memory inside a phase stalls the whole workgroup)
       {
         const int k8 = a.kp / 8, c8 = cv32 / 8, c4 = cv / 4;
-        const int nwe = a.expand ? cv * k8 : 0, nwp = a.nt * 16 * c8, nts = K * K * c4, total = nwe + nwp + nts + (a.expand ? 4 : 2) * c4;
+        const int nwe = a.expand ? cv * k8 : 0, nwp = SE && pass == 0 ? 0 : a.nt * 16 * c8, nts = K * K * c4, total = nwe + nwp + nts + (a.expand ? 4 : 2) * c4;
         for (int base = tid; base < total; base += BI_THREADS * BI_B) {
           f32x4 v[BI_B];
           unsigned dst[BI_B];   // byte offset in LDS; ~0u: nothing to store
@@ -273,7 +299,21 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
               act_apply_v(v, act);
               d[r] = f32x4{v[0], v[1], v[2], v[3]};
             }
+            if constexpr (SE) {
+              if (pass == 0) {   // the work item's own pixels, left to right: one partial per (row, strip) and channel
+                f32x4 s = d[0];
+#pragma unroll
+                for (int r = 1; r < BI_R; ++r)
+                  if (ox + r < a.tow) s += d[r];
+                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(Ds) + rest * CH + q * 4) = s;
+              } else {
+                const f32x4 g = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(bi_smem + a.o_gate) + c0 + q * 4);
+#pragma unroll
+                for (int r = 0; r < BI_R; ++r) d[r] *= g;
+              }
+            }
           }
+          if (SE && pass == 0) continue;
 #pragma unroll
           for (int r = 0; r < BI_R; ++r)
             if (ox + r < a.tow) {
@@ -283,8 +323,21 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
         }
       }
       __syncthreads();
+      if constexpr (SE) {
+        if (pass == 0) {   // ---- squeeze: the chunk's partials in row-major order, one thread per channel
+          const float* ps = reinterpret_cast<const float*>(Ds);
+          float* pooled = reinterpret_cast<float*>(bi_smem + a.o_pool);
+          const int rows = (a.tow + BI_R - 1) / BI_R * a.toh;
+          for (int c = tid; c < cv; c += BI_THREADS) {
+            float s = 0.f;
+#pragma unroll 8
+            for (int r = 0; r < rows; ++r) s += ps[r * CH + c];
+            pooled[c0 + c] = s;
+          }
+        }
+      }
       // ---- projection: accumulate the chunk
-      for (int ks = 0; ks < cv32 / 32; ++ks) {
+      for (int ks = 0; ks < (SE && pass == 0 ? 0 : cv32 / 32); ++ks) {
         bf16x8 b[MT];
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -303,6 +356,32 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
       __syncthreads();
     }
   }
+  if constexpr (SE) {
+    if (pass == 0) {   // ---- gate (csrc/se.hip k_se_mlp): the trailing barrier of the chunk loop has completed pooled
+      const float* pooled = reinterpret_cast<const float*>(bi_smem + a.o_pool);
+      float* gate = reinterpret_cast<float*>(bi_smem + a.o_gate);
+      float* hs = reinterpret_cast<float*>(bi_smem + a.o_hs);
+      // the partials have overwritten Ds: its padding rows are zeros again for the projection
+      for (int u = tid; u < a.tp16 * (dstr / 8); u += BI_THREADS) *reinterpret_cast<bf16x8*>(Ds + u * 8) = zero8;
+      for (int j = wave; j < a.se_hid; j += BI_WAVES) {
+        const float* w = a.w1p + (long)j * a.ldse;
+        float s = 0.f;
+#pragma unroll 4
+        for (int c = lane; c < a.ht; c += 64) s += w[c] * (pooled[c] * a.inv_hw);
+        s = wave_sum(s);
+        if (lane == 0) hs[j] = act_apply(s + a.b1[j], act);
+      }
+      __syncthreads();
+      for (int c = tid; c < a.ht; c += BI_THREADS) {
+        float s = a.b2p[c];
+#pragma unroll 8
+        for (int j = 0; j < a.se_hid; ++j) s += a.w2t[(long)j * a.ldse + c] * hs[j];
+        gate[c] = 1.f / (1.f + __expf(-s));
+      }
+      __syncthreads();
+    }
+  }
+  } while (SE && ++pass < 2);
 
   // ---- epilogue: raw sum rounded to bf16, bn_p, residual, one store
   const long oimg = (long)n * a.Ho * a.Wo;
@@ -334,9 +413,17 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const BiArgs a) {
 
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
+// bytes of the Ds + Wps region; with SE it also holds pass 0's fp32 partials, one [ch] row per (map row, strip)
+inline size_t bi_dw_bytes(bool se, int toh, int tow, int tp16, int nt, int ch) {
+  const size_t dw = (size_t)(tp16 + nt * 16) * (ch + 8) * 2, parts = se ? (size_t)((tow + BI_R - 1) / BI_R) * toh * ch * 4 : 0;
+  return dw > parts ? dw : parts;
+}
+
 // The COMPLETE accept / reject decision and the tiling, pure host arithmetic (no device query): the entry point and the predicate share it.
+// SE (atomnas_block_infer_se only): stride 1, expanding, the whole map in one workgroup, HT <= 4096, 1 <= se_hid <= 512.
 bool bi_plan(const BiShape& s, BiPlan& p) {
-  if (s.dtype != DT_BF16 || s.se) return false;
+  if (s.dtype != DT_BF16) return false;
+  if (s.se && (s.stride != 1 || !s.expand || s.se_hid < 1 || s.se_hid > 512)) return false;
   if (s.N < 1 || s.N > 65535 || s.H < 1 || s.W < 1 || (long)s.H * s.W > (1L << 24)) return false;
   if (s.stride != 1 && s.stride != 2) return false;
   if (s.act < ACT_NONE || s.act > ACT_SWISH) return false;
@@ -352,7 +439,7 @@ bool bi_plan(const BiShape& s, BiPlan& p) {
     kmax = k > kmax ? k : kmax;
     chmax = s.ch[i] > chmax ? s.ch[i] : chmax;
   }
-  if (end > 8192 || (!s.expand && end > s.inp)) return false;
+  if (end > 8192 || (!s.expand && end > s.inp) || (s.se && end > 4096)) return false;
   const int nt = (s.oup + 15) / 16;
   const int ntmax = nt <= 2 ? 2 : nt <= 4 ? 4 : nt <= 8 ? 8 : nt <= 12 ? 12 : 20;
   const int Ho = (s.H - 1) / s.stride + 1, Wo = (s.W - 1) / s.stride + 1;
@@ -361,6 +448,7 @@ bool bi_plan(const BiShape& s, BiPlan& p) {
   const int cand[6][2] = {{Ho, Wo}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}};
   for (int ci = 0; ci < 6; ++ci) {
     if (ci == 0 && (long)Ho * Wo > 256) continue;
+    if (s.se && ci) break;   // the squeeze is a reduction inside the workgroup: whole maps only
     const int toh = cand[ci][0] < Ho ? cand[ci][0] : Ho, tow = cand[ci][1] < Wo ? cand[ci][1] : Wo;
     const int tp16 = pad_to(toh * tow, 16), mt = (tp16 / 16 + BI_WAVES - 1) / BI_WAVES;
     if (mt > 2 || mt * ntmax > BI_MAX_ACC_TILES) continue;
@@ -368,8 +456,8 @@ bool bi_plan(const BiShape& s, BiPlan& p) {
     const int xr16 = pad_to((ih < s.H ? ih : s.H) * (iw < s.W ? iw : s.W), 16);   // the window clipped to the image
     const int erows = ipix + 8;   // slack: the last strip of a row reads up to 3 * stride pixels past it
     for (int ch = pad_to(chmax, 32) < 128 ? pad_to(chmax, 32) : 128; ch >= 32; ch -= 32) {
-      const size_t lds = (s.expand ? (size_t)(xr16 + ch) * (kp + 8) * 2 : 0) + (size_t)erows * (ch + 4) * 4 + (size_t)(tp16 + nt * 16) * (ch + 8) * 2 +
-                         (size_t)(kmax * kmax + 4) * ch * 4;
+      const size_t lds = (s.expand ? (size_t)(xr16 + ch) * (kp + 8) * 2 : 0) + (size_t)erows * (ch + 4) * 4 + bi_dw_bytes(s.se, toh, tow, tp16, nt, ch) +
+                         (size_t)(kmax * kmax + 4) * ch * 4 + (s.se ? (size_t)(2 * end + pad_to(s.se_hid, 4)) * 4 : 0);
       if (lds <= BI_LDS_BUDGET) {
         p.toh = toh, p.tow = tow, p.ch = ch, p.mt = mt, p.ntmax = ntmax, p.kmax = kmax, p.kp = kp, p.lds = lds;
         return true;
@@ -393,11 +481,28 @@ bool bi_profitable(const BiShape& s, const BiPlan& p) {
   return hidden * ipix <= 140000;
 }
 
-template <int MT, int NTMAX>
-int bi_run(const BiArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  (void)resident_per_cu(k_block_infer<MT, NTMAX>, BI_THREADS, lds);   // opts the kernel into its dynamic LDS size (cached)
-  hipLaunchKernelGGL((k_block_infer<MT, NTMAX>), grid, dim3(BI_THREADS), lds, st, a);
-  return check_launch("block_infer");
+// The same question for the SE instances (atomnas_block_infer_se_supported).  The two passes double the expand and tap work and every
+// image's workgroup reads both gate matrices, so the plain rule does not carry over.  Measured block by block on an MI355X for
+// AtomNAS-C+ at batches 1, 8 and 256, two runs (profiles/infer_bench_se.txt; the table is in DESIGN.md): the existing path costs
+// 0.17-0.19 ms per block at all three batches (its eight launches), the fused launch 0.10-0.14 ms on the 14x14 blocks of up to 192
+// padded hidden channels -- 1.22-1.85x, the two runs within 0.17x of each other -- and 0.23-1.31 ms on everything wider (7x7 with
+// 656-2336 channels 0.16-0.81x, 14x14 with 928 channels 0.31-0.53x): one workgroup per image walks the chunks twice, one after the
+// other.  The rule is the largest measured winner (192 channels x 400 window pixels, 96 outputs); nothing was measured between it
+// and the smallest loser (656 x 169), so that range stays on the existing path.  Batches: the per-block loop is bound by ISSUING the
+// existing path's launches, which a whole forward is only while the GPU keeps up: AtomNAS-C+ with these six blocks fused runs 1.29x
+// faster (eager; 1.29-1.59x as a graph) at batches 1-32 and 1.09x at 64, and 0.96-0.98x at 128 and 256 in both runs -- so N <= 64.
+bool bi_profitable_se(const BiShape& s, const BiPlan& p) {
+  long hidden = 0;
+  for (int i = 0; i < s.nseg; ++i) hidden += s.ch[i];
+  const long ipix = (long)(p.toh - 1 + p.kmax) * (p.tow - 1 + p.kmax);
+  return s.N <= 64 && s.oup <= 96 && hidden <= 192 && hidden * ipix <= 77000;
+}
+
+template <int MT, int NTMAX, bool SE>
+int bi_run(const typename BiArgsOf<SE>::type& a, dim3 grid, size_t lds, hipStream_t st) {
+  (void)resident_per_cu(k_block_infer<MT, NTMAX, SE>, BI_THREADS, lds);   // opts the kernel into its dynamic LDS size (cached)
+  hipLaunchKernelGGL((k_block_infer<MT, NTMAX, SE>), grid, dim3(BI_THREADS), lds, st, a);
+  return check_launch(SE ? "block_infer_se" : "block_infer");
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -408,48 +513,74 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 using namespace atomnas;
 
 static void bi_shape(BiShape& s, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
-                     int stride, int act, int expand, int residual, int se, int dtype) {
+                     int stride, int act, int expand, int residual, int se, int dtype, int se_hid = 0) {
   s.N = N, s.H = H, s.W = W, s.inp = inp, s.oup = oup, s.nseg = nseg, s.stride = stride, s.act = act, s.expand = expand != 0,
-  s.res = residual != 0, s.se = se != 0, s.dtype = dtype;
+  s.res = residual != 0, s.se = se != 0, s.dtype = dtype, s.se_hid = se_hid;
   for (int i = 0; i < nseg && i < BI_MAXSEG; ++i) s.off[i] = seg_off[i], s.ch[i] = seg_ch[i], s.k[i] = seg_k[i];
 }
 
+// The two predicates of atomnas_block_infer, which has no SE operands: se != 0 is outside, whatever atomnas_block_infer_se can do.
 extern "C" int atomnas_block_infer_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
                                         const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k || se) return 0;
   BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype);
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
   BiPlan p;
   return bi_plan(s, p) ? 1 : 0;
 }
 
 extern "C" int atomnas_block_infer_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
                                              const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k || se) return 0;
   BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype);
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
   BiPlan p;
   return bi_plan(s, p) && bi_profitable(s, p) ? 1 : 0;
 }
 
-extern "C" int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
-                                   const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale,
-                                   const float* d_shift, const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup,
-                                   int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
-                                   int residual, int dtype, void* stream) {
+extern "C" int atomnas_block_infer_se_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                           const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  BiShape s;
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 1, dtype, se_hid);
+  BiPlan p;
+  return bi_plan(s, p) ? 1 : 0;
+}
+
+extern "C" int atomnas_block_infer_se_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                                const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
+  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
+  BiShape s;
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 1, dtype, se_hid);
+  BiPlan p;
+  return bi_plan(s, p) && bi_profitable_se(s, p) ? 1 : 0;
+}
+
+// SE == false: atomnas_block_infer (the se_* arguments are unused); SE == true: atomnas_block_infer_se
+template <bool SE>
+static int bi_launch(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp, const float* const* taps,
+                     const float* e_scale, const float* e_shift, const float* d_scale, const float* d_shift, const float* p_scale,
+                     const float* p_shift, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                     const int* seg_k, int stride, int act, int expand, int residual, int dtype, const float* se_w1p, const float* se_w2t,
+                     const float* se_b1, const float* se_b2p, int se_hid, int ldse, void* stream) {
   ATOMNAS_REQUIRE(nseg >= 1 && nseg <= BI_MAXSEG && seg_off && seg_ch && seg_k && taps, "block_infer: 1..%d segments with offsets, channels, kernel sizes and taps", BI_MAXSEG);
   BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
+  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, SE, dtype, se_hid);
   BiPlan p;
-  ATOMNAS_REQUIRE(bi_plan(s, p), "block_infer: shape outside the fused kernel's envelope (ask atomnas_block_infer_runs first): N=%d %dx%d inp=%d oup=%d stride=%d dtype=%d",
-                  N, H, W, inp, oup, stride, dtype);
+  ATOMNAS_REQUIRE(bi_plan(s, p), "block_infer: shape outside the fused kernel's envelope (ask atomnas_block_infer%s_runs first): N=%d %dx%d inp=%d oup=%d stride=%d dtype=%d",
+                  SE ? "_se" : "", N, H, W, inp, oup, stride, dtype);
   ATOMNAS_REQUIRE(p.lds <= max_lds_bytes(), "block_infer: needs %zu bytes of LDS, the device grants %zu", p.lds, max_lds_bytes());
   ATOMNAS_REQUIRE(x && out && wp && d_scale && d_shift && p_scale && p_shift && (!s.expand || (we && e_scale && e_shift)), "block_infer: null operand");
   ATOMNAS_REQUIRE(ldx >= inp && ldx % 8 == 0 && ldo >= oup && ldo % 4 == 0 && aligned16(x) && ((uintptr_t)out & 7) == 0, "block_infer: activation pitch / alignment");
   const int hid = seg_off[nseg - 1] + seg_ch[nseg - 1];
   ATOMNAS_REQUIRE(ldwp >= hid && ldwp % 8 == 0 && aligned16(wp) && (!s.expand || (ldwe >= p.kp && ldwe % 8 == 0 && aligned16(we))), "block_infer: packed weight pitch / alignment");
   ATOMNAS_REQUIRE(aligned16(d_scale) && aligned16(d_shift) && aligned16(p_scale) && aligned16(p_shift) && aligned16(e_scale) && aligned16(e_shift), "block_infer: coefficient vectors must be 16-byte aligned");
-  BiArgs a = {};
+  if (SE) {
+    ATOMNAS_REQUIRE(se_w1p && se_w2t && se_b1 && se_b2p, "block_infer_se: null squeeze-and-excitation operand");
+    ATOMNAS_REQUIRE(aligned16(se_w1p) && aligned16(se_w2t) && aligned16(se_b1) && aligned16(se_b2p), "block_infer_se: the squeeze-and-excitation tensors must be 16-byte aligned");
+    ATOMNAS_REQUIRE(ldse >= hid, "block_infer_se: ldse = %d is below the %d padded hidden channels", ldse, hid);
+  }
+  typename BiArgsOf<SE>::type a = {};
   a.x = (const bf16_t*)x, a.out = (bf16_t*)out, a.we = (const bf16_t*)we, a.wp = (const bf16_t*)wp;
   a.es = e_scale, a.eb = e_shift, a.ds = d_scale, a.db = d_shift, a.ps = p_scale, a.pb = p_shift;
   a.ldx = ldx, a.ldo = ldo, a.ldwe = ldwe, a.ldwp = ldwp;
@@ -470,15 +601,39 @@ extern "C" int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, c
   a.o_xs = (unsigned)o, o += s.expand ? (size_t)a.xr16 * a.xstr * 2 : 0;
   a.o_wes = (unsigned)o, o += s.expand ? (size_t)p.ch * a.xstr * 2 : 0;
   a.o_es = (unsigned)o, o += (size_t)a.erows * a.estr * 4;
-  a.o_ds = (unsigned)o, o += (size_t)a.tp16 * a.dstr * 2;
-  a.o_wps = (unsigned)o, o += (size_t)a.nt * 16 * a.dstr * 2;
+  a.o_ds = (unsigned)o, a.o_wps = (unsigned)(o + (size_t)a.tp16 * a.dstr * 2), o += bi_dw_bytes(SE, p.toh, p.tow, a.tp16, a.nt, p.ch);
   a.o_ts = (unsigned)o, o += (size_t)p.kmax * p.kmax * p.ch * 4;
   a.o_cs = (unsigned)o, o += (size_t)4 * p.ch * 4;
+  if constexpr (SE) {
+    a.w1p = se_w1p, a.w2t = se_w2t, a.b1 = se_b1, a.b2p = se_b2p, a.se_hid = se_hid, a.ldse = ldse, a.ht = hid, a.inv_hw = 1.0f / (float)(H * W);
+    a.o_pool = (unsigned)o, o += (size_t)hid * 4;
+    a.o_gate = (unsigned)o, o += (size_t)hid * 4;
+    a.o_hs = (unsigned)o, o += (size_t)pad_to(se_hid, 4) * 4;
+  }
   ATOMNAS_REQUIRE(o == p.lds, "block_infer: LDS layout (%zu) and plan (%zu) disagree", o, p.lds);
   const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)N);
   hipStream_t st = (hipStream_t)stream;
-#define X(MT, NT) if (p.mt == MT && p.ntmax == NT) return bi_run<MT, NT>(a, grid, p.lds, st);
+#define X(MT, NT) if (p.mt == MT && p.ntmax == NT) return bi_run<MT, NT, SE>(a, grid, p.lds, st);
   X(1, 2) X(1, 4) X(1, 8) X(1, 12) X(1, 20) X(2, 2) X(2, 4) X(2, 8) X(2, 12)
 #undef X
   ATOMNAS_REQUIRE(false, "block_infer: no instance for %d x %d accumulator tiles", p.mt, p.ntmax);
+}
+
+extern "C" int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
+                                   const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale,
+                                   const float* d_shift, const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup,
+                                   int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
+                                   int residual, int dtype, void* stream) {
+  return bi_launch<false>(x, ldx, out, ldo, we, ldwe, wp, ldwp, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, nseg,
+                          seg_off, seg_ch, seg_k, stride, act, expand, residual, dtype, nullptr, nullptr, nullptr, nullptr, 0, 0, stream);
+}
+
+extern "C" int atomnas_block_infer_se(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
+                                      const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale,
+                                      const float* d_shift, const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup,
+                                      int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
+                                      int residual, int dtype, const float* se_w1p, const float* se_w2t, const float* se_b1,
+                                      const float* se_b2p, int se_hid, int ldse, void* stream) {
+  return bi_launch<true>(x, ldx, out, ldo, we, ldwe, wp, ldwp, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, nseg,
+                         seg_off, seg_ch, seg_k, stride, act, expand, residual, dtype, se_w1p, se_w2t, se_b1, se_b2p, se_hid, ldse, stream);
 }

@@ -3,9 +3,11 @@
 The training decomposition of a block (functional.block_forward) writes the 6x-wide hidden maps to HBM between its GEMMs and
 re-derives the BatchNorm coefficients on every call, because the backward pass and the batch statistics need them.  In evaluation
 neither exists: compile_for_inference folds the three BatchNorms of a block into scale / shift vectors ONCE, snapshots the packed
-weights, and runs the block through atomnas_block_infer (csrc/block_infer.hip), which keeps the hidden maps on chip.  Everything
-else -- the stem, blocks with Squeeze-and-Excitation, shapes outside the kernel's envelope, the fused tail -- runs the existing HIP
-path unchanged.  Opt-in: nothing calls this module unless asked to (`fused_inference` in the yaml / CLI, tools/infer_bench.py).
+weights, and runs the block through atomnas_block_infer (csrc/block_infer.hip), which keeps the hidden maps on chip.  A block with
+Squeeze-and-Excitation goes through atomnas_block_infer_se where one workgroup owns its whole map (stride 1, at most 256 pixels,
+expanding): there the squeeze is a reduction inside the workgroup.  Everything else -- the stem, the other SE blocks, shapes outside
+the kernel's envelope, the fused tail -- runs the existing HIP path unchanged.  Opt-in: nothing calls this module unless asked to
+(`fused_inference` in the yaml / CLI, tools/infer_bench.py).
 
     net = compile_for_inference(model.eval())          # model: a _HipModel on the GPU, bf16 compute dtype
     logits = net(images)
@@ -21,14 +23,16 @@ from . import functional as AF
 from . import ops, runtime
 
 
-# Which blocks leave the existing path: "measured" -- those the kernel runs AND measured faster for (atomnas_block_infer_supported), the
-# default; "all" -- every block the kernel can run (atomnas_block_infer_runs): tests and tools/infer_bench.py, which have to run the
-# kernel on the shapes the measured policy keeps away from it.  Read when a model is compiled / refreshed.
+# Which blocks leave the existing path: "measured" -- those the kernel runs AND measured faster for (atomnas_block_infer_supported,
+# atomnas_block_infer_se_supported), the default; "all" -- every block the kernel can run (atomnas_block_infer_runs / _se_runs): tests and
+# tools/infer_bench.py, which have to run the kernel on the shapes the measured policy keeps away from it.  Read when a model is
+# compiled / refreshed.
 POLICY = "measured"
 
 
 class FusedBlock:
-    """Snapshot of one block for atomnas_block_infer: packed bf16 weights, fp32 taps, folded BatchNorm coefficients."""
+    """Snapshot of one block for atomnas_block_infer / atomnas_block_infer_se: packed bf16 weights, fp32 taps, folded BatchNorm
+    coefficients and, with Squeeze-and-Excitation, the gate's packed fp32 dense layers."""
 
     def __init__(self, name, module):
         self.name, self.module = name, module
@@ -46,9 +50,19 @@ class FusedBlock:
         be = AF.bn_forward_coeffs(pl.bne, None, 0, dev) if pl.expand else None
         bd, bp = AF.bn_forward_coeffs(pl.bnd, None, 0, dev), AF.bn_forward_coeffs(pl.bnp, None, 0, dev)
         self.coeffs = (be.scale if be else None, be.shift if be else None, bd.scale, bd.shift, bp.scale, bp.shift)
+        self.se = bool(pl.se)
+        self.se_hid = int(pl.se_hid) if self.se else 0
+        self.se_tensors = [t.clone() for t in (pl.se_w1p, pl.se_w2t, pl.se_b1, pl.se_b2p)] if self.se else []
+
+    def tensors(self):
+        """every snapshot tensor (None where the block has none), in a fixed order: what _rewrite copies in place"""
+        return [self.we, self.wp] + self.taps + list(self.coeffs) + self.se_tensors
 
     def supported(self, N, H, W, profitable=None):
         profitable = POLICY != "all" if profitable is None else profitable
+        if self.se:
+            return ops.block_infer_se_supported(N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, self.stride, self.act,
+                                                self.expand, self.res, self.se_hid, torch.bfloat16, profitable=profitable)
         return ops.block_infer_supported(N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, self.stride, self.act, self.expand,
                                          self.res, False, torch.bfloat16, profitable=profitable)
 
@@ -59,8 +73,12 @@ class FusedBlock:
         s = self.stride
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
         out = torch.empty(N * Ho * Wo, self.oup, dtype=torch.bfloat16, device=x.device)
-        ops.block_infer(x2d, out, self.we, self.wp, self.taps, *self.coeffs, N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k,
-                        s, self.act, self.expand, self.res)
+        args = (x2d, out, self.we, self.wp, self.taps, *self.coeffs, N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, s, self.act,
+                self.expand, self.res)
+        if self.se:
+            ops.block_infer_se(*args, *self.se_tensors, self.se_hid)
+        else:
+            ops.block_infer(*args)
         return AF.to_4d(out, N, Ho, Wo, self.oup)
 
 
@@ -81,7 +99,7 @@ def block_shapes(model, batch_size=1, input_size=None):
             continue
         out.append((name, dict(N=batch_size, H=H, W=W, inp=pl.inp, oup=pl.oup, seg_off=list(pl.seg), seg_ch=[pl.segpad(h) for h in pl.hid],
                                seg_k=list(pl.ks), stride=pl.stride, act=AF.act_code(info["act"]), expand=bool(pl.expand), residual=bool(pl.res),
-                               se=bool(pl.se))))
+                               se=bool(pl.se), se_hid=int(pl.se_hid) if pl.se else 0)))
         H, W = (H - 1) // pl.stride + 1, (W - 1) // pl.stride + 1
     return out
 
@@ -91,9 +109,13 @@ def _block_reason(m):
     pl = runtime.plan_of(m)
     if pl.nb == 0:
         return "all branches pruned: the block is the identity"
-    if pl.se:
-        return "squeeze-and-excitation needs the whole map between depthwise and projection"
+    if pl.se and pl.se_act != pl.act:
+        return "squeeze-and-excitation with an activation of its own (the fused kernel applies the block's inside the gate)"
     return None
+
+
+SE_ENVELOPE = ("squeeze-and-excitation is fused only where one workgroup owns the whole map (stride 1, expanding, <= 256 pixels): "
+               "the squeeze needs it (atomnas_block_infer_se_runs)")
 
 
 class InferenceModel(nn.Module):
@@ -152,18 +174,26 @@ class InferenceModel(nn.Module):
                 if fb.supported(N, H, W):
                     self._fused[id(m)] = fb
                 else:
-                    why = ("outside the kernel's envelope (atomnas_block_infer_runs)" if not fb.supported(N, H, W, False) else
-                           "measured slower than the existing path for shapes of this kind (atomnas_block_infer_supported)")
+                    why = self._why_not(fb, N, H, W)
             self._plan.append((name, "fallback", why) if why else (name, "fused", ""))
             if runtime.plan_of(m).nb:
                 H, W = (H - 1) // s + 1, (W - 1) // s + 1
         self._ok = {}
 
     @staticmethod
+    def _why_not(fb, N, H, W):
+        if not fb.supported(N, H, W, False):
+            return SE_ENVELOPE if fb.se else "outside the kernel's envelope (atomnas_block_infer_runs)"
+        if fb.se:
+            return ("squeeze-and-excitation: the two-pass kernel did not measure faster than the existing path for shapes of this kind "
+                    "(atomnas_block_infer_se_supported)")
+        return "measured slower than the existing path for shapes of this kind (atomnas_block_infer_supported)"
+
+    @staticmethod
     def _rewrite(fb):
         """new values into the tensors a captured graph points at"""
         new = FusedBlock(fb.name, fb.module)
-        for dst, src in zip([fb.we, fb.wp] + fb.taps + list(fb.coeffs), [new.we, new.wp] + new.taps + list(new.coeffs)):
+        for dst, src in zip(fb.tensors(), new.tensors()):
             if dst is not None:
                 dst.copy_(src)
 
@@ -188,6 +218,8 @@ class InferenceModel(nn.Module):
             ok = self._ok.get(key)
             if ok is None:
                 ok = self._ok[key] = fb.supported(y.shape[0], y.shape[2], y.shape[3])
+                if self._bare:   # a block on its own was planned at a nominal map: its plan follows the map it is called with
+                    self._plan = [(fb.name, "fused", "") if ok else (fb.name, "fallback", self._why_not(fb, y.shape[0], y.shape[2], y.shape[3]))]
             if ok:
                 return fb(y)
         return blk(y)   # the existing path: SE blocks, shapes outside the envelope

@@ -421,6 +421,33 @@ int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* 
                         const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off,
                         const int* seg_ch, const int* seg_k, int stride, int act, int expand, int residual, int dtype, void* stream);
 
+/* ---- inference: the same block WITH Squeeze-and-Excitation (InvertedResidualChannelsFused with se_ratio) as one launch (additive in
+ *      ABI 9), where ONE workgroup owns the whole map:
+ *        A = act(bn_d(bf16(dw_k(act(bn_e(We . x))))))   fp32, not rounded;   s[c] = mean over the H*W pixels of A[:, c]
+ *        gate = sigmoid(W2 . act(W1 . s + b1) + b2)     fp32, act = the block's activation
+ *        out = [x +] bn_p(bf16(Wp . bf16(gate * A)))
+ *   The kernel walks the hidden channels twice (squeeze, then project: the expand and tap work is recomputed, nothing is spilled); the
+ *   pixel sum has a fixed order, no atomics, image i's output depends on image i alone.  All arguments of atomnas_block_infer, then
+ *   the gate in the packed fp32 layouts of atomnas_se_mlp_fwd over the padded hidden layout HT = seg_off[nseg-1] + seg_ch[nseg-1]:
+ *   se_w1p, se_w2t [se_hid][ldse >= HT] (channels contiguous, ZEROS in padding columns), se_b1 [se_hid], se_b2p [HT]; 16-byte aligned.
+ * atomnas_block_infer_se_runs: pure host predicate, 1 when atomnas_block_infer_se can run the shape: everything
+ *   atomnas_block_infer_runs asks AND stride 1, expand != 0, H*W <= 256 with the whole map in one workgroup's LDS, HT <= 4096,
+ *   1 <= se_hid <= 512.
+ * atomnas_block_infer_se_supported: the same AND measured faster than the launch-per-stage path at this N (csrc/block_infer.hip
+ *   bi_profitable_se; DESIGN.md lists the measurements): N <= 64, oup <= 96, at most 192 padded hidden channels and
+ *   hidden channels x window pixels <= 77,000 -- the 14x14 stride-1 blocks of the searched "+" networks.
+ * atomnas_block_infer_runs / _supported keep answering 0 for se != 0: they speak for atomnas_block_infer, which has no SE operands. */
+int atomnas_block_infer_se_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
+                                int stride, int act, int expand, int residual, int se_hid, int dtype);
+int atomnas_block_infer_se_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                     const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype);
+int atomnas_block_infer_se(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
+                           const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale, const float* d_shift,
+                           const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off,
+                           const int* seg_ch, const int* seg_k, int stride, int act, int expand, int residual, int dtype,
+                           const float* se_w1p, const float* se_w2t, const float* se_b1, const float* se_b2p, int se_hid, int ldse,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
