@@ -413,15 +413,58 @@ __global__ __launch_bounds__(BI_THREADS) void k_block_infer(const typename BiArg
 
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
-// bytes of the Ds + Wps region; with SE it also holds pass 0's fp32 partials, one [ch] row per (map row, strip)
-inline size_t bi_dw_bytes(bool se, int toh, int tow, int tp16, int nt, int ch) {
-  const size_t dw = (size_t)(tp16 + nt * 16) * (ch + 8) * 2, parts = se ? (size_t)((tow + BI_R - 1) / BI_R) * toh * ch * 4 : 0;
-  return dw > parts ? dw : parts;
+// the shape arguments of the C entries as they arrive
+struct BiDims { int N, H, W, inp, oup, nseg; const int *seg_off, *seg_ch, *seg_k; int stride, act, expand, residual, dtype; };
+
+// -> s; false where the segment lists cannot even be read (the one guard of the predicates and of the launch)
+bool bi_shape(BiShape& s, const BiDims& d, bool se, int se_hid) {
+  if (d.nseg < 1 || d.nseg > BI_MAXSEG || !d.seg_off || !d.seg_ch || !d.seg_k) return false;
+  s.N = d.N, s.H = d.H, s.W = d.W, s.inp = d.inp, s.oup = d.oup, s.nseg = d.nseg, s.stride = d.stride, s.act = d.act, s.expand = d.expand != 0,
+  s.res = d.residual != 0, s.se = se, s.dtype = d.dtype, s.se_hid = se_hid;
+  for (int i = 0; i < d.nseg; ++i) s.off[i] = d.seg_off[i], s.ch[i] = d.seg_ch[i], s.k[i] = d.seg_k[i];
+  return true;
+}
+
+// What one workgroup works on and where it keeps it: the tile geometry and the byte offset of every LDS array of k_block_infer, for a
+// tile of toh x tow output pixels and chunks of ch hidden channels.  The ONLY place either is computed: bi_plan takes `total` to the
+// budget, bi_launch copies the rest into BiArgs.
+struct BiLayout {
+  int ih, iw, ipix, erows, xr16, tpix, tp16, nt, ht;   // ht: the padded hidden width, where the last segment ends
+  int xstr, estr, dstr;
+  unsigned o_xs, o_wes, o_es, o_ds, o_wps, o_ts, o_cs, o_pool, o_gate, o_hs;
+  size_t total;
+};
+
+BiLayout bi_layout(const BiShape& s, int kmax, int kp, int toh, int tow, int ch) {
+  BiLayout l = {};
+  l.ih = (toh - 1) * s.stride + kmax, l.iw = (tow - 1) * s.stride + kmax, l.ipix = l.ih * l.iw;
+  l.erows = l.ipix + 8;   // slack: the last strip of a row reads up to 3 * stride pixels past it
+  l.xr16 = pad_to((l.ih < s.H ? l.ih : s.H) * (l.iw < s.W ? l.iw : s.W), 16);   // the window clipped to the image
+  l.tpix = toh * tow, l.tp16 = pad_to(l.tpix, 16), l.nt = (s.oup + 15) / 16;
+  l.xstr = kp + 8, l.estr = ch + 4, l.dstr = ch + 8;
+  l.ht = s.off[s.nseg - 1] + s.ch[s.nseg - 1];
+  // the Ds + Wps region; with SE it also holds pass 0's fp32 partials, one [ch] row per (map row, strip)
+  const size_t ds = (size_t)l.tp16 * l.dstr * 2, dw = ds + (size_t)l.nt * 16 * l.dstr * 2;
+  const size_t parts = s.se ? (size_t)((tow + BI_R - 1) / BI_R) * toh * ch * 4 : 0;
+  size_t o = 0;
+  l.o_xs = (unsigned)o, o += s.expand ? (size_t)l.xr16 * l.xstr * 2 : 0;
+  l.o_wes = (unsigned)o, o += s.expand ? (size_t)ch * l.xstr * 2 : 0;
+  l.o_es = (unsigned)o, o += (size_t)l.erows * l.estr * 4;
+  l.o_ds = (unsigned)o, l.o_wps = (unsigned)(o + ds), o += dw > parts ? dw : parts;
+  l.o_ts = (unsigned)o, o += (size_t)kmax * kmax * ch * 4;
+  l.o_cs = (unsigned)o, o += (size_t)4 * ch * 4;
+  if (s.se) {
+    l.o_pool = (unsigned)o, o += (size_t)l.ht * 4;
+    l.o_gate = (unsigned)o, o += (size_t)l.ht * 4;
+    l.o_hs = (unsigned)o, o += (size_t)pad_to(s.se_hid, 4) * 4;
+  }
+  l.total = o;
+  return l;
 }
 
 // The COMPLETE accept / reject decision and the tiling, pure host arithmetic (no device query): the entry point and the predicate share it.
 // SE (atomnas_block_infer_se only): stride 1, expanding, the whole map in one workgroup, HT <= 4096, 1 <= se_hid <= 512.
-bool bi_plan(const BiShape& s, BiPlan& p) {
+bool bi_plan(const BiShape& s, BiPlan& p, BiLayout& l) {
   if (s.dtype != DT_BF16) return false;
   if (s.se && (s.stride != 1 || !s.expand || s.se_hid < 1 || s.se_hid > 512)) return false;
   if (s.N < 1 || s.N > 65535 || s.H < 1 || s.W < 1 || (long)s.H * s.W > (1L << 24)) return false;
@@ -450,16 +493,12 @@ bool bi_plan(const BiShape& s, BiPlan& p) {
     if (ci == 0 && (long)Ho * Wo > 256) continue;
     if (s.se && ci) break;   // the squeeze is a reduction inside the workgroup: whole maps only
     const int toh = cand[ci][0] < Ho ? cand[ci][0] : Ho, tow = cand[ci][1] < Wo ? cand[ci][1] : Wo;
-    const int tp16 = pad_to(toh * tow, 16), mt = (tp16 / 16 + BI_WAVES - 1) / BI_WAVES;
+    const int mt = (toh * tow + 16 * BI_WAVES - 1) / (16 * BI_WAVES);   // 16-pixel MFMA row tiles per wave
     if (mt > 2 || mt * ntmax > BI_MAX_ACC_TILES) continue;
-    const int ih = (toh - 1) * s.stride + kmax, iw = (tow - 1) * s.stride + kmax, ipix = ih * iw;
-    const int xr16 = pad_to((ih < s.H ? ih : s.H) * (iw < s.W ? iw : s.W), 16);   // the window clipped to the image
-    const int erows = ipix + 8;   // slack: the last strip of a row reads up to 3 * stride pixels past it
     for (int ch = pad_to(chmax, 32) < 128 ? pad_to(chmax, 32) : 128; ch >= 32; ch -= 32) {
-      const size_t lds = (s.expand ? (size_t)(xr16 + ch) * (kp + 8) * 2 : 0) + (size_t)erows * (ch + 4) * 4 + bi_dw_bytes(s.se, toh, tow, tp16, nt, ch) +
-                         (size_t)(kmax * kmax + 4) * ch * 4 + (s.se ? (size_t)(2 * end + pad_to(s.se_hid, 4)) * 4 : 0);
-      if (lds <= BI_LDS_BUDGET) {
-        p.toh = toh, p.tow = tow, p.ch = ch, p.mt = mt, p.ntmax = ntmax, p.kmax = kmax, p.kp = kp, p.lds = lds;
+      l = bi_layout(s, kmax, kp, toh, tow, ch);
+      if (l.total <= BI_LDS_BUDGET) {
+        p.toh = toh, p.tow = tow, p.ch = ch, p.mt = mt, p.ntmax = ntmax, p.kmax = kmax, p.kp = kp, p.lds = l.total;
         return true;
       }
     }
@@ -467,18 +506,22 @@ bool bi_plan(const BiShape& s, BiPlan& p) {
   return false;
 }
 
+// padded hidden channels; x the window's pixels (BiLayout::ipix): the hidden work of one workgroup, which both rules below are stated in
+long bi_hidden(const BiShape& s) {
+  long hidden = 0;
+  for (int i = 0; i < s.nseg; ++i) hidden += s.ch[i];
+  return hidden;
+}
+
 // Where the kernel is FASTER than the launch-per-stage decomposition (functional.block_forward in eval mode), measured block by block
 // on an MI355X at batch 256 (profiles/infer_bench.txt; the table is in DESIGN.md): expanding blocks whose whole map sits in one
 // workgroup (stride 1, no expand recompute) with little hidden work -- padded hidden channels x window pixels <= 140,000, the searched
 // networks' 14x14 and 7x7 stages -- and an output of at most 192 channels.  Everything else measured slower (the chunk loop of one
 // workgroup per CU does not hide its phases behind each other) and is reported as unsupported, so that it takes the existing path.
-bool bi_profitable(const BiShape& s, const BiPlan& p) {
+bool bi_profitable(const BiShape& s, const BiPlan& p, const BiLayout& l) {
   const int Ho = (s.H - 1) / s.stride + 1, Wo = (s.W - 1) / s.stride + 1;
   if (!s.expand || s.stride != 1 || p.toh != Ho || p.tow != Wo || s.oup > 192) return false;
-  long hidden = 0;
-  for (int i = 0; i < s.nseg; ++i) hidden += s.ch[i];
-  const long ipix = (long)((p.toh - 1) * s.stride + p.kmax) * ((p.tow - 1) * s.stride + p.kmax);
-  return hidden * ipix <= 140000;
+  return bi_hidden(s) * l.ipix <= 140000;
 }
 
 // The same question for the SE instances (atomnas_block_infer_se_supported).  The two passes double the expand and tap work and every
@@ -491,11 +534,16 @@ bool bi_profitable(const BiShape& s, const BiPlan& p) {
 // and the smallest loser (656 x 169), so that range stays on the existing path.  Batches: the per-block loop is bound by ISSUING the
 // existing path's launches, which a whole forward is only while the GPU keeps up: AtomNAS-C+ with these six blocks fused runs 1.29x
 // faster (eager; 1.29-1.59x as a graph) at batches 1-32 and 1.09x at 64, and 0.96-0.98x at 128 and 256 in both runs -- so N <= 64.
-bool bi_profitable_se(const BiShape& s, const BiPlan& p) {
-  long hidden = 0;
-  for (int i = 0; i < s.nseg; ++i) hidden += s.ch[i];
-  const long ipix = (long)(p.toh - 1 + p.kmax) * (p.tow - 1 + p.kmax);
-  return s.N <= 64 && s.oup <= 96 && hidden <= 192 && hidden * ipix <= 77000;
+bool bi_profitable_se(const BiShape& s, const BiLayout& l) {
+  const long hidden = bi_hidden(s);
+  return s.N <= 64 && s.oup <= 96 && hidden <= 192 && hidden * l.ipix <= 77000;
+}
+
+// The body of all four predicates: the shape, its plan and, where asked, whether the kernel measured faster
+int bi_answer(const BiDims& d, bool se, int se_hid, bool profitable) {
+  BiShape s; BiPlan p; BiLayout l;
+  if (!bi_shape(s, d, se, se_hid) || !bi_plan(s, p, l)) return 0;
+  return !profitable || (se ? bi_profitable_se(s, l) : bi_profitable(s, p, l)) ? 1 : 0;
 }
 
 template <int MT, int NTMAX, bool SE>
@@ -507,111 +555,52 @@ int bi_run(const typename BiArgsOf<SE>::type& a, dim3 grid, size_t lds, hipStrea
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-}  // namespace
-}  // namespace atomnas
+// the operands of atomnas_block_infer in the order of its arguments, and those atomnas_block_infer_se adds
+struct BiOperands {
+  const void* x; int ldx; void* out; int ldo; const void* we; int ldwe; const void* wp; int ldwp;
+  const float* const* taps;
+  const float *e_scale, *e_shift, *d_scale, *d_shift, *p_scale, *p_shift;
+};
+struct BiGate { const float *w1p, *w2t, *b1, *b2p; int se_hid, ldse; };
 
-using namespace atomnas;
-
-static void bi_shape(BiShape& s, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch, const int* seg_k,
-                     int stride, int act, int expand, int residual, int se, int dtype, int se_hid = 0) {
-  s.N = N, s.H = H, s.W = W, s.inp = inp, s.oup = oup, s.nseg = nseg, s.stride = stride, s.act = act, s.expand = expand != 0,
-  s.res = residual != 0, s.se = se != 0, s.dtype = dtype, s.se_hid = se_hid;
-  for (int i = 0; i < nseg && i < BI_MAXSEG; ++i) s.off[i] = seg_off[i], s.ch[i] = seg_ch[i], s.k[i] = seg_k[i];
-}
-
-// The two predicates of atomnas_block_infer, which has no SE operands: se != 0 is outside, whatever atomnas_block_infer_se can do.
-extern "C" int atomnas_block_infer_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
-                                        const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k || se) return 0;
-  BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
-  BiPlan p;
-  return bi_plan(s, p) ? 1 : 0;
-}
-
-extern "C" int atomnas_block_infer_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
-                                             const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k || se) return 0;
-  BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 0, dtype);
-  BiPlan p;
-  return bi_plan(s, p) && bi_profitable(s, p) ? 1 : 0;
-}
-
-extern "C" int atomnas_block_infer_se_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
-                                           const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
-  BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 1, dtype, se_hid);
-  BiPlan p;
-  return bi_plan(s, p) ? 1 : 0;
-}
-
-extern "C" int atomnas_block_infer_se_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
-                                                const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
-  if (nseg < 1 || nseg > BI_MAXSEG || !seg_off || !seg_ch || !seg_k) return 0;
-  BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, 1, dtype, se_hid);
-  BiPlan p;
-  return bi_plan(s, p) && bi_profitable_se(s, p) ? 1 : 0;
-}
-
-// SE == false: atomnas_block_infer (the se_* arguments are unused); SE == true: atomnas_block_infer_se
+// SE == false: atomnas_block_infer (g is unused); SE == true: atomnas_block_infer_se
 template <bool SE>
-static int bi_launch(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp, const float* const* taps,
-                     const float* e_scale, const float* e_shift, const float* d_scale, const float* d_shift, const float* p_scale,
-                     const float* p_shift, int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
-                     const int* seg_k, int stride, int act, int expand, int residual, int dtype, const float* se_w1p, const float* se_w2t,
-                     const float* se_b1, const float* se_b2p, int se_hid, int ldse, void* stream) {
-  ATOMNAS_REQUIRE(nseg >= 1 && nseg <= BI_MAXSEG && seg_off && seg_ch && seg_k && taps, "block_infer: 1..%d segments with offsets, channels, kernel sizes and taps", BI_MAXSEG);
-  BiShape s;
-  bi_shape(s, N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, SE, dtype, se_hid);
-  BiPlan p;
-  ATOMNAS_REQUIRE(bi_plan(s, p), "block_infer: shape outside the fused kernel's envelope (ask atomnas_block_infer%s_runs first): N=%d %dx%d inp=%d oup=%d stride=%d dtype=%d",
-                  SE ? "_se" : "", N, H, W, inp, oup, stride, dtype);
+int bi_launch(const BiDims& d, const BiOperands& o, const BiGate& g, void* stream) {
+  BiShape s; BiPlan p; BiLayout l;
+  ATOMNAS_REQUIRE(bi_shape(s, d, SE, g.se_hid) && o.taps, "block_infer: 1..%d segments with offsets, channels, kernel sizes and taps", BI_MAXSEG);
+  ATOMNAS_REQUIRE(bi_plan(s, p, l), "block_infer: shape outside the fused kernel's envelope (ask atomnas_block_infer%s_runs first): N=%d %dx%d inp=%d oup=%d stride=%d dtype=%d",
+                  SE ? "_se" : "", s.N, s.H, s.W, s.inp, s.oup, s.stride, s.dtype);
   ATOMNAS_REQUIRE(p.lds <= max_lds_bytes(), "block_infer: needs %zu bytes of LDS, the device grants %zu", p.lds, max_lds_bytes());
-  ATOMNAS_REQUIRE(x && out && wp && d_scale && d_shift && p_scale && p_shift && (!s.expand || (we && e_scale && e_shift)), "block_infer: null operand");
-  ATOMNAS_REQUIRE(ldx >= inp && ldx % 8 == 0 && ldo >= oup && ldo % 4 == 0 && aligned16(x) && ((uintptr_t)out & 7) == 0, "block_infer: activation pitch / alignment");
-  const int hid = seg_off[nseg - 1] + seg_ch[nseg - 1];
-  ATOMNAS_REQUIRE(ldwp >= hid && ldwp % 8 == 0 && aligned16(wp) && (!s.expand || (ldwe >= p.kp && ldwe % 8 == 0 && aligned16(we))), "block_infer: packed weight pitch / alignment");
-  ATOMNAS_REQUIRE(aligned16(d_scale) && aligned16(d_shift) && aligned16(p_scale) && aligned16(p_shift) && aligned16(e_scale) && aligned16(e_shift), "block_infer: coefficient vectors must be 16-byte aligned");
+  ATOMNAS_REQUIRE(o.x && o.out && o.wp && o.d_scale && o.d_shift && o.p_scale && o.p_shift && (!s.expand || (o.we && o.e_scale && o.e_shift)), "block_infer: null operand");
+  ATOMNAS_REQUIRE(o.ldx >= s.inp && o.ldx % 8 == 0 && o.ldo >= s.oup && o.ldo % 4 == 0 && aligned16(o.x) && ((uintptr_t)o.out & 7) == 0, "block_infer: activation pitch / alignment");
+  ATOMNAS_REQUIRE(o.ldwp >= l.ht && o.ldwp % 8 == 0 && aligned16(o.wp) && (!s.expand || (o.ldwe >= p.kp && o.ldwe % 8 == 0 && aligned16(o.we))), "block_infer: packed weight pitch / alignment");
+  ATOMNAS_REQUIRE(aligned16(o.d_scale) && aligned16(o.d_shift) && aligned16(o.p_scale) && aligned16(o.p_shift) && aligned16(o.e_scale) && aligned16(o.e_shift), "block_infer: coefficient vectors must be 16-byte aligned");
   if (SE) {
-    ATOMNAS_REQUIRE(se_w1p && se_w2t && se_b1 && se_b2p, "block_infer_se: null squeeze-and-excitation operand");
-    ATOMNAS_REQUIRE(aligned16(se_w1p) && aligned16(se_w2t) && aligned16(se_b1) && aligned16(se_b2p), "block_infer_se: the squeeze-and-excitation tensors must be 16-byte aligned");
-    ATOMNAS_REQUIRE(ldse >= hid, "block_infer_se: ldse = %d is below the %d padded hidden channels", ldse, hid);
+    ATOMNAS_REQUIRE(g.w1p && g.w2t && g.b1 && g.b2p, "block_infer_se: null squeeze-and-excitation operand");
+    ATOMNAS_REQUIRE(aligned16(g.w1p) && aligned16(g.w2t) && aligned16(g.b1) && aligned16(g.b2p), "block_infer_se: the squeeze-and-excitation tensors must be 16-byte aligned");
+    ATOMNAS_REQUIRE(g.ldse >= l.ht, "block_infer_se: ldse = %d is below the %d padded hidden channels", g.ldse, l.ht);
   }
   typename BiArgsOf<SE>::type a = {};
-  a.x = (const bf16_t*)x, a.out = (bf16_t*)out, a.we = (const bf16_t*)we, a.wp = (const bf16_t*)wp;
-  a.es = e_scale, a.eb = e_shift, a.ds = d_scale, a.db = d_shift, a.ps = p_scale, a.pb = p_shift;
-  a.ldx = ldx, a.ldo = ldo, a.ldwe = ldwe, a.ldwp = ldwp;
-  a.N = N, a.H = H, a.W = W, a.Ho = (H - 1) / stride + 1, a.Wo = (W - 1) / stride + 1, a.inp = inp, a.oup = oup, a.stride = stride, a.act = act,
-  a.expand = s.expand, a.res = s.res, a.nseg = nseg;
-  for (int i = 0; i < nseg; ++i) {
-    ATOMNAS_REQUIRE(taps[i] && aligned16(taps[i]), "block_infer: taps of segment %d missing or not 16-byte aligned", i);
-    a.seg[i] = BiSeg{taps[i], seg_off[i], seg_ch[i], seg_k[i], seg_ch[i]};
+  a.x = (const bf16_t*)o.x, a.out = (bf16_t*)o.out, a.we = (const bf16_t*)o.we, a.wp = (const bf16_t*)o.wp;
+  a.es = o.e_scale, a.eb = o.e_shift, a.ds = o.d_scale, a.db = o.d_shift, a.ps = o.p_scale, a.pb = o.p_shift;
+  a.ldx = o.ldx, a.ldo = o.ldo, a.ldwe = o.ldwe, a.ldwp = o.ldwp;
+  a.N = s.N, a.H = s.H, a.W = s.W, a.Ho = (s.H - 1) / s.stride + 1, a.Wo = (s.W - 1) / s.stride + 1, a.inp = s.inp, a.oup = s.oup, a.stride = s.stride,
+  a.act = s.act, a.expand = s.expand, a.res = s.res, a.nseg = s.nseg;
+  for (int i = 0; i < s.nseg; ++i) {
+    ATOMNAS_REQUIRE(o.taps[i] && aligned16(o.taps[i]), "block_infer: taps of segment %d missing or not 16-byte aligned", i);
+    a.seg[i] = BiSeg{o.taps[i], s.off[i], s.ch[i], s.k[i], s.ch[i]};
   }
   a.toh = p.toh, a.tow = p.tow, a.kmax = p.kmax, a.kp = p.kp, a.ch = p.ch;
   a.tiles_x = (a.Wo + p.tow - 1) / p.tow;
   const int tiles_y = (a.Ho + p.toh - 1) / p.toh;
-  a.ih = (p.toh - 1) * stride + p.kmax, a.iw = (p.tow - 1) * stride + p.kmax, a.ipix = a.ih * a.iw, a.erows = a.ipix + 8;
-  a.xr16 = pad_to((a.ih < H ? a.ih : H) * (a.iw < W ? a.iw : W), 16);
-  a.tpix = p.toh * p.tow, a.tp16 = pad_to(a.tpix, 16), a.nt = (oup + 15) / 16;
-  a.xstr = p.kp + 8, a.estr = p.ch + 4, a.dstr = p.ch + 8;
-  size_t o = 0;
-  a.o_xs = (unsigned)o, o += s.expand ? (size_t)a.xr16 * a.xstr * 2 : 0;
-  a.o_wes = (unsigned)o, o += s.expand ? (size_t)p.ch * a.xstr * 2 : 0;
-  a.o_es = (unsigned)o, o += (size_t)a.erows * a.estr * 4;
-  a.o_ds = (unsigned)o, a.o_wps = (unsigned)(o + (size_t)a.tp16 * a.dstr * 2), o += bi_dw_bytes(SE, p.toh, p.tow, a.tp16, a.nt, p.ch);
-  a.o_ts = (unsigned)o, o += (size_t)p.kmax * p.kmax * p.ch * 4;
-  a.o_cs = (unsigned)o, o += (size_t)4 * p.ch * 4;
+  a.ih = l.ih, a.iw = l.iw, a.ipix = l.ipix, a.erows = l.erows, a.xr16 = l.xr16, a.tpix = l.tpix, a.tp16 = l.tp16, a.nt = l.nt;
+  a.xstr = l.xstr, a.estr = l.estr, a.dstr = l.dstr;
+  a.o_xs = l.o_xs, a.o_wes = l.o_wes, a.o_es = l.o_es, a.o_ds = l.o_ds, a.o_wps = l.o_wps, a.o_ts = l.o_ts, a.o_cs = l.o_cs;
   if constexpr (SE) {
-    a.w1p = se_w1p, a.w2t = se_w2t, a.b1 = se_b1, a.b2p = se_b2p, a.se_hid = se_hid, a.ldse = ldse, a.ht = hid, a.inv_hw = 1.0f / (float)(H * W);
-    a.o_pool = (unsigned)o, o += (size_t)hid * 4;
-    a.o_gate = (unsigned)o, o += (size_t)hid * 4;
-    a.o_hs = (unsigned)o, o += (size_t)pad_to(se_hid, 4) * 4;
+    a.w1p = g.w1p, a.w2t = g.w2t, a.b1 = g.b1, a.b2p = g.b2p, a.se_hid = g.se_hid, a.ldse = g.ldse, a.ht = l.ht, a.inv_hw = 1.0f / (float)(s.H * s.W);
+    a.o_pool = l.o_pool, a.o_gate = l.o_gate, a.o_hs = l.o_hs;
   }
-  ATOMNAS_REQUIRE(o == p.lds, "block_infer: LDS layout (%zu) and plan (%zu) disagree", o, p.lds);
-  const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)N);
+  const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)s.N);
   hipStream_t st = (hipStream_t)stream;
 #define X(MT, NT) if (p.mt == MT && p.ntmax == NT) return bi_run<MT, NT, SE>(a, grid, p.lds, st);
   X(1, 2) X(1, 4) X(1, 8) X(1, 12) X(1, 20) X(2, 2) X(2, 4) X(2, 8) X(2, 12)
@@ -619,13 +608,42 @@ static int bi_launch(const void* x, int ldx, void* out, int ldo, const void* we,
   ATOMNAS_REQUIRE(false, "block_infer: no instance for %d x %d accumulator tiles", p.mt, p.ntmax);
 }
 
+}  // namespace
+}  // namespace atomnas
+
+using namespace atomnas;
+
+// The shape arguments of an entry as BiDims, the operands as BiOperands: both in the order of the entry's own arguments
+#define BI_DIMS BiDims{N, H, W, inp, oup, nseg, seg_off, seg_ch, seg_k, stride, act, expand, residual, dtype}
+#define BI_OPERANDS BiOperands{x, ldx, out, ldo, we, ldwe, wp, ldwp, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift}
+
+// The two predicates of atomnas_block_infer, which has no SE operands: se != 0 is outside, whatever atomnas_block_infer_se can do.
+extern "C" int atomnas_block_infer_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                        const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
+  return se ? 0 : bi_answer(BI_DIMS, false, 0, false);
+}
+
+extern "C" int atomnas_block_infer_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                             const int* seg_k, int stride, int act, int expand, int residual, int se, int dtype) {
+  return se ? 0 : bi_answer(BI_DIMS, false, 0, true);
+}
+
+extern "C" int atomnas_block_infer_se_runs(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                           const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
+  return bi_answer(BI_DIMS, true, se_hid, false);
+}
+
+extern "C" int atomnas_block_infer_se_supported(int N, int H, int W, int inp, int oup, int nseg, const int* seg_off, const int* seg_ch,
+                                                const int* seg_k, int stride, int act, int expand, int residual, int se_hid, int dtype) {
+  return bi_answer(BI_DIMS, true, se_hid, true);
+}
+
 extern "C" int atomnas_block_infer(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
                                    const float* const* taps, const float* e_scale, const float* e_shift, const float* d_scale,
                                    const float* d_shift, const float* p_scale, const float* p_shift, int N, int H, int W, int inp, int oup,
                                    int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
                                    int residual, int dtype, void* stream) {
-  return bi_launch<false>(x, ldx, out, ldo, we, ldwe, wp, ldwp, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, nseg,
-                          seg_off, seg_ch, seg_k, stride, act, expand, residual, dtype, nullptr, nullptr, nullptr, nullptr, 0, 0, stream);
+  return bi_launch<false>(BI_DIMS, BI_OPERANDS, BiGate{}, stream);
 }
 
 extern "C" int atomnas_block_infer_se(const void* x, int ldx, void* out, int ldo, const void* we, int ldwe, const void* wp, int ldwp,
@@ -634,6 +652,5 @@ extern "C" int atomnas_block_infer_se(const void* x, int ldx, void* out, int ldo
                                       int nseg, const int* seg_off, const int* seg_ch, const int* seg_k, int stride, int act, int expand,
                                       int residual, int dtype, const float* se_w1p, const float* se_w2t, const float* se_b1,
                                       const float* se_b2p, int se_hid, int ldse, void* stream) {
-  return bi_launch<true>(x, ldx, out, ldo, we, ldwe, wp, ldwp, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, nseg,
-                         seg_off, seg_ch, seg_k, stride, act, expand, residual, dtype, se_w1p, se_w2t, se_b1, se_b2p, se_hid, ldse, stream);
+  return bi_launch<true>(BI_DIMS, BI_OPERANDS, BiGate{se_w1p, se_w2t, se_b1, se_b2p, se_hid, ldse}, stream);
 }

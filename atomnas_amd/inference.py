@@ -16,6 +16,8 @@ the kernel's envelope, the fused tail -- runs the existing HIP path unchanged.  
 The snapshot does NOT follow in-place updates of the fused blocks' weights or BatchNorm statistics: call refresh().  Modules on the
 fallback path read the live parameters, as they always did.
 """
+import functools
+
 import torch
 from torch import nn
 
@@ -30,28 +32,44 @@ from . import ops, runtime
 POLICY = "measured"
 
 
+def block_shape(pl, act):
+    """The shape of a block from its plan, the ONE derivation: the keyword arguments of ops.block_infer_supported /
+    block_infer_se_supported behind N, H, W.  Integer arithmetic on the plan's scalar fields: an arena layout's plan will do (its
+    activation code comes from the layout's info, a bound plan carries its own)."""
+    return dict(inp=pl.inp, oup=pl.oup, seg_off=list(pl.seg), seg_ch=[pl.segpad(h) for h in pl.hid], seg_k=list(pl.ks), stride=pl.stride,
+                act=int(act), expand=bool(pl.expand), residual=bool(pl.res), se=bool(pl.se), se_hid=int(pl.se_hid) if pl.se else 0)
+
+
+def walk_maps(blocks, plan_for, size):
+    """(name, module, plan_for(module), H, W) for every (name, module) of `blocks`, H x W the map the block sees: a square of side
+    `size` carried through the strides, the ONE walk.  A block without a plan or with every branch pruned (the identity) leaves it as it is."""
+    H = W = size
+    for name, m in blocks:
+        pl = plan_for(m)
+        yield name, m, pl, H, W
+        if pl is not None and pl.nb:
+            H, W = (H - 1) // pl.stride + 1, (W - 1) // pl.stride + 1
+
+
 class FusedBlock:
-    """Snapshot of one block for atomnas_block_infer / atomnas_block_infer_se: packed bf16 weights, fp32 taps, folded BatchNorm
-    coefficients and, with Squeeze-and-Excitation, the gate's packed fp32 dense layers."""
+    """Snapshot of one block for atomnas_block_infer / atomnas_block_infer_se: its shape (block_shape), packed bf16 weights, fp32 taps,
+    folded BatchNorm coefficients and, with Squeeze-and-Excitation, the gate's packed fp32 dense layers."""
 
     def __init__(self, name, module):
         self.name, self.module = name, module
         self.snapshot()
 
     def snapshot(self):
-        pl = runtime.plan_of(self.module)
+        self.pl = pl = runtime.plan_of(self.module)
         dev = pl.Wp_pack.device
-        self.pl = pl
-        self.inp, self.oup, self.stride, self.act, self.expand, self.res = pl.inp, pl.oup, pl.stride, int(pl.act), bool(pl.expand), bool(pl.res)
-        self.seg_off, self.seg_ch, self.seg_k = list(pl.seg), [pl.segpad(h) for h in pl.hid], list(pl.ks)
+        self.shape = block_shape(pl, pl.act)
+        self.se, self.se_hid = self.shape["se"], self.shape["se_hid"]
         self.we = pl.We_pack.clone() if pl.expand else None
         self.wp = pl.Wp_pack.clone()
         self.taps = [t.clone() for t in pl.taps]
         be = AF.bn_forward_coeffs(pl.bne, None, 0, dev) if pl.expand else None
         bd, bp = AF.bn_forward_coeffs(pl.bnd, None, 0, dev), AF.bn_forward_coeffs(pl.bnp, None, 0, dev)
         self.coeffs = (be.scale if be else None, be.shift if be else None, bd.scale, bd.shift, bp.scale, bp.shift)
-        self.se = bool(pl.se)
-        self.se_hid = int(pl.se_hid) if self.se else 0
         self.se_tensors = [t.clone() for t in (pl.se_w1p, pl.se_w2t, pl.se_b1, pl.se_b2p)] if self.se else []
 
     def tensors(self):
@@ -59,27 +77,20 @@ class FusedBlock:
         return [self.we, self.wp] + self.taps + list(self.coeffs) + self.se_tensors
 
     def supported(self, N, H, W, profitable=None):
-        profitable = POLICY != "all" if profitable is None else profitable
-        if self.se:
-            return ops.block_infer_se_supported(N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, self.stride, self.act,
-                                                self.expand, self.res, self.se_hid, torch.bfloat16, profitable=profitable)
-        return ops.block_infer_supported(N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, self.stride, self.act, self.expand,
-                                         self.res, False, torch.bfloat16, profitable=profitable)
+        fn = ops.block_infer_se_supported if self.se else ops.block_infer_supported
+        return fn(N=N, H=H, W=W, dtype=torch.bfloat16, profitable=POLICY != "all" if profitable is None else profitable, **self.shape)
 
     def __call__(self, x):
         x2d, (N, H, W, C) = AF.to_2d(x, torch.bfloat16)
-        if C != self.inp:
-            raise ValueError("block %s expects %d input channels, got %d" % (self.name, self.inp, C))
-        s = self.stride
+        sh = self.shape
+        if C != sh["inp"]:
+            raise ValueError("block %s expects %d input channels, got %d" % (self.name, sh["inp"], C))
+        s = sh["stride"]
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-        out = torch.empty(N * Ho * Wo, self.oup, dtype=torch.bfloat16, device=x.device)
-        args = (x2d, out, self.we, self.wp, self.taps, *self.coeffs, N, H, W, self.inp, self.oup, self.seg_off, self.seg_ch, self.seg_k, s, self.act,
-                self.expand, self.res)
-        if self.se:
-            ops.block_infer_se(*args, *self.se_tensors, self.se_hid)
-        else:
-            ops.block_infer(*args)
-        return AF.to_4d(out, N, Ho, Wo, self.oup)
+        out = torch.empty(N * Ho * Wo, sh["oup"], dtype=torch.bfloat16, device=x.device)
+        ops.block_infer(x2d, out, self.we, self.wp, self.taps, *self.coeffs, N, H, W, sh["inp"], sh["oup"], sh["seg_off"], sh["seg_ch"], sh["seg_k"],
+                        s, sh["act"], sh["expand"], sh["residual"], *self.se_tensors, se_hid=self.se_hid)
+        return AF.to_4d(out, N, Ho, Wo, sh["oup"])
 
 
 def block_shapes(model, batch_size=1, input_size=None):
@@ -87,35 +98,34 @@ def block_shapes(model, batch_size=1, input_size=None):
     ops.block_infer_supported, from the arena layout alone (integer arithmetic on module attributes: works on a CPU model, no library
     call).  Blocks whose branches are all pruned are skipped."""
     lay = runtime.arena_layout(model, getattr(model, "compute_dtype", torch.bfloat16))
-    plans = {id(m): (pl, info) for m, pl, info in lay.plans if isinstance(pl, runtime.BlockPlan)}
+    plans = {id(m): pl for m, pl, _ in lay.plans if isinstance(pl, runtime.BlockPlan)}
+    acts = {id(m): AF.act_code(info["act"]) for m, _, info in lay.plans if id(m) in plans}
     size = input_size or getattr(model, "input_size", 224)
-    H = W = (size - 1) // 2 + 1   # behind the stride-2 stem
-    out = []
-    for name, m in list(model.features.named_children())[1:-2]:
-        if id(m) not in plans:
-            continue
-        pl, info = plans[id(m)]
-        if pl.nb == 0:
-            continue
-        out.append((name, dict(N=batch_size, H=H, W=W, inp=pl.inp, oup=pl.oup, seg_off=list(pl.seg), seg_ch=[pl.segpad(h) for h in pl.hid],
-                               seg_k=list(pl.ks), stride=pl.stride, act=AF.act_code(info["act"]), expand=bool(pl.expand), residual=bool(pl.res),
-                               se=bool(pl.se), se_hid=int(pl.se_hid) if pl.se else 0)))
-        H, W = (H - 1) // pl.stride + 1, (W - 1) // pl.stride + 1
-    return out
+    walk = walk_maps(list(model.features.named_children())[1:-2], lambda m: plans.get(id(m)), (size - 1) // 2 + 1)   # behind the stride-2 stem
+    return [(name, dict(N=batch_size, H=H, W=W, **block_shape(pl, acts[id(m)]))) for name, m, pl, H, W in walk if pl is not None and pl.nb]
 
 
-def _block_reason(m):
-    """None when the block can take the fused kernel at all, else why not"""
-    pl = runtime.plan_of(m)
+def fallback_reason(pl, supported=None):
+    """Why a block stays on the existing path, None when nothing keeps it from the fused kernel.  pl: its bound plan (None: the module
+    is no atomic block); supported: the block's predicates at the batch and map in question, FusedBlock.supported with N, H, W bound --
+    without it only what the plan alone decides is looked at (a block that fails there has no snapshot to ask)."""
+    if pl is None:
+        return "not an atomic block"
     if pl.nb == 0:
         return "all branches pruned: the block is the identity"
     if pl.se and pl.se_act != pl.act:
         return "squeeze-and-excitation with an activation of its own (the fused kernel applies the block's inside the gate)"
-    return None
-
-
-SE_ENVELOPE = ("squeeze-and-excitation is fused only where one workgroup owns the whole map (stride 1, expanding, <= 256 pixels): "
-               "the squeeze needs it (atomnas_block_infer_se_runs)")
+    if supported is None or supported():
+        return None
+    if not supported(profitable=False):
+        if pl.se:
+            return ("squeeze-and-excitation is fused only where one workgroup owns the whole map (stride 1, expanding, <= 256 pixels): "
+                    "the squeeze needs it (atomnas_block_infer_se_runs)")
+        return "outside the kernel's envelope (atomnas_block_infer_runs)"
+    if pl.se:
+        return ("squeeze-and-excitation: the two-pass kernel did not measure faster than the existing path for shapes of this kind "
+                "(atomnas_block_infer_se_supported)")
+    return "measured slower than the existing path for shapes of this kind (atomnas_block_infer_supported)"
 
 
 class InferenceModel(nn.Module):
@@ -154,40 +164,23 @@ class InferenceModel(nn.Module):
         mgr = runtime.manager_of(model)
         mgr.ensure()
         mgr.pack()
-        size = getattr(model, "input_size", 224)
-        H = W = 14 if self._bare else (size - 1) // 2 + 1   # behind the stride-2 stem; a bare block: a nominal map, every call re-checks
-        N = self.batch_size or 1
         old = {fb.name: fb for fb in getattr(self, "_fused", {}).values()}
         self._fused, self._plan = {}, []
-        for name, m in self._blocks():
-            if not isinstance(m, self._block_types):
-                self._plan.append((name, "fallback", "not an atomic block"))
-                continue
-            why = _block_reason(m)
-            s = m.stride
+        plan_for = lambda m: runtime.plan_of(m) if isinstance(m, self._block_types) else None
+        size = 14 if self._bare else (getattr(model, "input_size", 224) - 1) // 2 + 1   # behind the stride-2 stem; a bare block: a nominal map, every call re-checks
+        for name, m, pl, H, W in walk_maps(self._blocks(), plan_for, size):
+            why = fallback_reason(pl)
             if why is None:
                 fb = old.get(name)
                 if fb is not None and self._graph is not None:
                     self._rewrite(fb)
                 else:
                     fb = FusedBlock(name, m)
-                if fb.supported(N, H, W):
+                why = fallback_reason(pl, functools.partial(fb.supported, self.batch_size or 1, H, W))
+                if why is None:
                     self._fused[id(m)] = fb
-                else:
-                    why = self._why_not(fb, N, H, W)
             self._plan.append((name, "fallback", why) if why else (name, "fused", ""))
-            if runtime.plan_of(m).nb:
-                H, W = (H - 1) // s + 1, (W - 1) // s + 1
         self._ok = {}
-
-    @staticmethod
-    def _why_not(fb, N, H, W):
-        if not fb.supported(N, H, W, False):
-            return SE_ENVELOPE if fb.se else "outside the kernel's envelope (atomnas_block_infer_runs)"
-        if fb.se:
-            return ("squeeze-and-excitation: the two-pass kernel did not measure faster than the existing path for shapes of this kind "
-                    "(atomnas_block_infer_se_supported)")
-        return "measured slower than the existing path for shapes of this kind (atomnas_block_infer_supported)"
 
     @staticmethod
     def _rewrite(fb):
@@ -217,9 +210,10 @@ class InferenceModel(nn.Module):
             key = (id(blk),) + tuple(y.shape)
             ok = self._ok.get(key)
             if ok is None:
-                ok = self._ok[key] = fb.supported(y.shape[0], y.shape[2], y.shape[3])
+                why = fallback_reason(fb.pl, functools.partial(fb.supported, y.shape[0], y.shape[2], y.shape[3]))
+                ok = self._ok[key] = why is None
                 if self._bare:   # a block on its own was planned at a nominal map: its plan follows the map it is called with
-                    self._plan = [(fb.name, "fused", "") if ok else (fb.name, "fallback", self._why_not(fb, y.shape[0], y.shape[2], y.shape[3]))]
+                    self._plan = [(fb.name, "fallback", why) if why else (fb.name, "fused", "")]
             if ok:
                 return fb(y)
         return blk(y)   # the existing path: SE blocks, shapes outside the envelope

@@ -391,32 +391,23 @@ def _ints(v):
     return (ctypes.c_int * len(v))(*[int(i) for i in v])
 
 
+def _block_infer_answer(se, profitable, N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, se_arg, dtype):
+    """one of the four host predicates of csrc/block_infer.hip (se_arg: the entry's `se` / `se_hid` argument)"""
+    n = len(seg_off)
+    if n == 0 or len(seg_ch) != n or len(seg_k) != n:
+        return False
+    fn = getattr(_lib.load(), "atomnas_block_infer%s_%s" % ("_se" if se else "", "supported" if profitable else "runs"))
+    return bool(fn(int(N), int(H), int(W), int(inp), int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act),
+                   int(bool(expand)), int(bool(residual)), int(se_arg), dtype if isinstance(dtype, int) else dt_code(dtype)))
+
+
 def block_infer_supported(N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, se, dtype, profitable=True, se_hid=0):
     """whether atomnas_block_infer serves this block (a host predicate: no GPU needed) -- and, with profitable, measured faster than the
     existing path for shapes of its kind (atomnas_block_infer_supported; without: atomnas_block_infer_runs).  seg_*: per branch segment
     its first hidden channel, its padded channel count and its kernel size; dtype: a torch dtype or the C ABI's code.  se: always False
     (atomnas_block_infer has no SE operands: ask block_infer_se_supported); se_hid is accepted, so that a shape dict of
     inference.block_shapes can be passed whole, and ignored"""
-    n = len(seg_off)
-    if n == 0 or len(seg_ch) != n or len(seg_k) != n:
-        return False
-    fn = _lib.load().atomnas_block_infer_supported if profitable else _lib.load().atomnas_block_infer_runs
-    return bool(fn(int(N), int(H), int(W), int(inp), int(oup), n, _ints(seg_off), _ints(seg_ch),
-                                                          _ints(seg_k), int(stride), int(act), int(bool(expand)), int(bool(residual)),
-                                                          int(bool(se)), dtype if isinstance(dtype, int) else dt_code(dtype)))
-
-
-def block_infer(x, out, we_pack, wp_pack, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, seg_off, seg_ch,
-                seg_k, stride, act, expand, residual):
-    """One launch for a whole atomic block in eval mode (include/atomnas_hip.h, csrc/block_infer.hip): x [N*H*W, ld] -> out [N*Ho*Wo, ld],
-    bf16; the BatchNorms as folded scale / shift vectors over the padded hidden layout; taps: one fp32 [k*k][seg_ch] tensor per segment"""
-    _chk_cuda(x, out, wp_pack, *taps)
-    n = len(seg_off)
-    tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in taps])
-    call("atomnas_block_infer", _p(x), _ld(x), _p(out), _ld(out), _p(we_pack), we_pack.stride(0) if we_pack is not None else 0, _p(wp_pack),
-         wp_pack.stride(0), tp, _p(e_scale), _p(e_shift), _p(d_scale), _p(d_shift), _p(p_scale), _p(p_shift), int(N), int(H), int(W), int(inp),
-         int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act), int(bool(expand)), int(bool(residual)),
-         dt_code(x.dtype), _stream())
+    return _block_infer_answer(False, profitable, N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, bool(se), dtype)
 
 
 def block_infer_se_supported(N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, se_hid, dtype, profitable=True, se=True):
@@ -424,27 +415,24 @@ def block_infer_se_supported(N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, 
     most 256 pixels in one workgroup, 1 <= se_hid <= 512 -- and, with profitable, measured faster at this N
     (atomnas_block_infer_se_supported; without: atomnas_block_infer_se_runs).  se is accepted, so that a shape dict of
     inference.block_shapes can be passed whole: a block without SE is not this entry's"""
-    if not se:
-        return False
-    n = len(seg_off)
-    if n == 0 or len(seg_ch) != n or len(seg_k) != n:
-        return False
-    fn = _lib.load().atomnas_block_infer_se_supported if profitable else _lib.load().atomnas_block_infer_se_runs
-    return bool(fn(int(N), int(H), int(W), int(inp), int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act),
-                   int(bool(expand)), int(bool(residual)), int(se_hid), dtype if isinstance(dtype, int) else dt_code(dtype)))
+    return bool(se) and _block_infer_answer(True, profitable, N, H, W, inp, oup, seg_off, seg_ch, seg_k, stride, act, expand, residual, se_hid, dtype)
 
 
-def block_infer_se(x, out, we_pack, wp_pack, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, seg_off, seg_ch,
-                   seg_k, stride, act, expand, residual, se_w1p, se_w2t, se_b1, se_b2p, se_hid):
-    """block_infer for a block with Squeeze-and-Excitation: the gate's dense layers as the packed fp32 [se_hid][HT] tensors of se_mlp_fwd
-    (HT = the padded hidden width), se_b1 [se_hid], se_b2p [HT]"""
-    _chk_cuda(x, out, wp_pack, se_w1p, se_w2t, se_b1, se_b2p, *taps)
+def block_infer(x, out, we_pack, wp_pack, taps, e_scale, e_shift, d_scale, d_shift, p_scale, p_shift, N, H, W, inp, oup, seg_off, seg_ch,
+                seg_k, stride, act, expand, residual, se_w1p=None, se_w2t=None, se_b1=None, se_b2p=None, se_hid=0):
+    """One launch for a whole atomic block in eval mode (include/atomnas_hip.h, csrc/block_infer.hip): x [N*H*W, ld] -> out [N*Ho*Wo, ld],
+    bf16; the BatchNorms as folded scale / shift vectors over the padded hidden layout; taps: one fp32 [k*k][seg_ch] tensor per segment.
+    With the se_* group (atomnas_block_infer_se) the block has Squeeze-and-Excitation: the gate's dense layers as the packed fp32
+    [se_hid][HT] tensors of se_mlp_fwd (HT = the padded hidden width), se_b1 [se_hid], se_b2p [HT]"""
+    gate = () if se_w1p is None else (se_w1p, se_w2t, se_b1, se_b2p)
+    _chk_cuda(x, out, wp_pack, *gate, *taps)
     n = len(seg_off)
     tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in taps])
-    call("atomnas_block_infer_se", _p(x), _ld(x), _p(out), _ld(out), _p(we_pack), we_pack.stride(0) if we_pack is not None else 0, _p(wp_pack),
-         wp_pack.stride(0), tp, _p(e_scale), _p(e_shift), _p(d_scale), _p(d_shift), _p(p_scale), _p(p_shift), int(N), int(H), int(W), int(inp),
-         int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act), int(bool(expand)), int(bool(residual)),
-         dt_code(x.dtype), _p(se_w1p), _p(se_w2t), _p(se_b1), _p(se_b2p), int(se_hid), se_w1p.numel() // int(se_hid), _stream())
+    se_args = [_p(t) for t in gate] + [int(se_hid), se_w1p.numel() // int(se_hid)] if gate else []
+    call("atomnas_block_infer_se" if gate else "atomnas_block_infer", _p(x), _ld(x), _p(out), _ld(out), _p(we_pack),
+         we_pack.stride(0) if we_pack is not None else 0, _p(wp_pack), wp_pack.stride(0), tp, _p(e_scale), _p(e_shift), _p(d_scale), _p(d_shift),
+         _p(p_scale), _p(p_shift), int(N), int(H), int(W), int(inp), int(oup), n, _ints(seg_off), _ints(seg_ch), _ints(seg_k), int(stride), int(act),
+         int(bool(expand)), int(bool(residual)), dt_code(x.dtype), *se_args, _stream())
 
 
 def bnbwd_apply(g, x, c1, c2, c3, y, M, C):

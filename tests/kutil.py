@@ -1,4 +1,6 @@
 """Helpers shared by the GPU kernel parity tests: NHWC-padded buffers <-> NCHW tensors, tolerances."""
+import collections
+
 import torch
 
 
@@ -56,6 +58,37 @@ def assert_close(name, got, ref, rtol, atol, outlier_frac=0.0, rel_l2=None):
         raise AssertionError("%s: %d/%d mismatches, max err %.4g (ref max %.4g), first at %s got %.6g ref %.6g" %
                              (name, int(bad.sum()), bad.numel(), float(err.max()), float(ref.abs().max()), idx,
                               float(got[tuple(idx)]), float(ref[tuple(idx)])))
+
+
+# ---- module-level parity tests (tests/test_block_gpu.py, tests/test_block_infer_gpu.py, tests/test_block_infer_se_gpu.py)
+def randomize(module, seed):
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for n, p in module.named_parameters():
+            if p.dim() == 1 and "bias" not in n:      # BN gamma
+                p.copy_(torch.rand(p.shape, generator=g) + 0.5)
+            elif p.dim() == 1:
+                p.copy_(torch.randn(p.shape, generator=g) * 0.2)
+            else:
+                fan = p[0].numel()
+                p.copy_(torch.randn(p.shape, generator=g) / fan ** 0.5)
+        for n, b in module.named_buffers():
+            if "running_mean" in n:
+                b.copy_(torch.randn(b.shape, generator=g) * 0.1)
+            elif "running_var" in n:
+                b.copy_(torch.rand(b.shape, generator=g) + 0.5)
+
+
+def sd64(module, prefix=""):
+    return collections.OrderedDict((prefix + k, (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()))
+                                   for k, v in module.state_dict().items())
+
+
+def widen_bn(module, factor):
+    with torch.no_grad():
+        for n, p in module.named_parameters():
+            if p.dim() == 1 and "bias" not in n:
+                p.mul_(factor)
 
 
 # ---- deterministic, RNG-free fills shared with tools/make_golden.py (inputs of the golden fixtures are regenerated, not stored)

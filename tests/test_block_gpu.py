@@ -3,7 +3,6 @@
 fp32 storage must match the oracle (float64 evaluation of the same state_dict) to accumulation-order tolerance; bf16
 storage to the tolerance of bf16 activations (stated per test).  Parameter gradients are read from p.grad (gradient arena).
 """
-import collections
 import os
 import sys
 
@@ -15,31 +14,9 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import atomnas_oracle as orc  # noqa: E402
 
 from kutil import assert_close, bf16_storage  # noqa: E402
+from kutil import randomize as _randomize, sd64 as _sd64, widen_bn as _widen_bn  # noqa: E402  (other test modules and tools import these names from here)
 
 pytestmark = pytest.mark.gpu
-
-
-def _randomize(module, seed):
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:      # BN gamma
-                p.copy_(torch.rand(p.shape, generator=g) + 0.5)
-            elif p.dim() == 1:
-                p.copy_(torch.randn(p.shape, generator=g) * 0.2)
-            else:
-                fan = p[0].numel()
-                p.copy_(torch.randn(p.shape, generator=g) / fan ** 0.5)
-        for n, b in module.named_buffers():
-            if "running_mean" in n:
-                b.copy_(torch.randn(b.shape, generator=g) * 0.1)
-            elif "running_var" in n:
-                b.copy_(torch.rand(b.shape, generator=g) + 0.5)
-
-
-def _sd64(module, prefix=""):
-    return collections.OrderedDict((prefix + k, (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()))
-                                   for k, v in module.state_dict().items())
 
 
 BLOCKS = [
@@ -52,13 +29,6 @@ BLOCKS = [
     dict(inp=8, oup=8, stride=1, channels=[16, 16, 16], ks=[3, 5, 7], expand=True, act="nn.ReLU6"),
     dict(inp=8, oup=16, stride=2, channels=[12, 20, 7], ks=[3, 5, 7], expand=True, act="nn.ReLU6"),
 ]
-
-
-def _widen_bn(module, factor):
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:
-                p.mul_(factor)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

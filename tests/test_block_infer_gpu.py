@@ -9,7 +9,6 @@ The kernel is checked on every shape it can RUN (inference.POLICY = "all", atomn
 the shapes the kernel measured faster for (atomnas_block_infer_supported): most of the maps below -- the multi-tile and
 stride-2 ones that carry the seam and padding checks -- then take the existing path and would not exercise the kernel at all.
 """
-import collections
 import os
 import re
 import sys
@@ -21,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import atomnas_oracle as orc  # noqa: E402
 
-from kutil import assert_close  # noqa: E402
+from kutil import assert_close, randomize, sd64, widen_bn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BOUND = dict(rtol=1.6e-2, atol=1.6e-2, outlier_frac=0.002)
@@ -32,36 +31,6 @@ BN_KW = {"momentum": 0.01, "eps": 1e-3}
 def _every_shape_the_kernel_runs(monkeypatch):
     import atomnas_amd.inference as inf
     monkeypatch.setattr(inf, "POLICY", "all")
-
-
-def _randomize(module, seed):   # tests/test_block_gpu.py::_randomize
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:      # BN gamma
-                p.copy_(torch.rand(p.shape, generator=g) + 0.5)
-            elif p.dim() == 1:
-                p.copy_(torch.randn(p.shape, generator=g) * 0.2)
-            else:
-                fan = p[0].numel()
-                p.copy_(torch.randn(p.shape, generator=g) / fan ** 0.5)
-        for n, b in module.named_buffers():
-            if "running_mean" in n:
-                b.copy_(torch.randn(b.shape, generator=g) * 0.1)
-            elif "running_var" in n:
-                b.copy_(torch.rand(b.shape, generator=g) + 0.5)
-
-
-def _sd64(module, prefix=""):
-    return collections.OrderedDict((prefix + k, (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()))
-                                   for k, v in module.state_dict().items())
-
-
-def _widen_bn(module, factor):
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:
-                p.mul_(factor)
 
 
 def _expand_bn_bias(module, value):
@@ -117,9 +86,9 @@ def _build(cfg, se_ratio=None):
     else:
         blk = mb.InvertedResidualChannels(*args, active_fn=mb.get_active_fn(act_name), batch_norm_kwargs=BN_KW)
     blk.compute_dtype = torch.bfloat16
-    _randomize(blk, 7)
+    randomize(blk, 7)
     if act_name == "nn.ReLU6":
-        _widen_bn(blk, 4.0)
+        widen_bn(blk, 4.0)
     if "ebias" in cfg:
         _expand_bn_bias(blk, cfg["ebias"])
     return blk, act_name
@@ -133,7 +102,7 @@ def _case(cfg):
     spec = dict(eps=1e-3, momentum=0.01, act=act_name)
     ob = dict(name="blk", inp=cfg["inp"], oup=cfg["oup"], stride=cfg["stride"], expand=cfg.get("expand", True), channels=cfg["channels"],
               ks=cfg["ks"], res=cfg["stride"] == 1 and cfg["inp"] == cfg["oup"], fused=bool(cfg.get("fused")), se=False)
-    ref = orc.block_forward(x.bfloat16().double(), _sd64(blk, "blk."), ob, False, spec, q=orc.Bf16Storage)
+    ref = orc.block_forward(x.bfloat16().double(), sd64(blk, "blk."), ob, False, spec, q=orc.Bf16Storage)
     return blk.cuda().eval(), x, ref
 
 
@@ -239,7 +208,7 @@ TINY = dict(num_classes=10, input_size=64, input_channel=16, last_channel=64, wi
 def _tiny():
     from atomnas_amd.models import mobilenet_supernet as ms
     model = ms.Model(**TINY)
-    _randomize(model, 5)
+    randomize(model, 5)
     return model
 
 
@@ -248,7 +217,7 @@ def test_whole_model(gpu_lib):
     every block fused, graph replay bit-equal to the eager compiled model on two inputs, snapshot semantics of refresh()"""
     from atomnas_amd.inference import compile_for_inference
     model = _tiny()
-    sd = _sd64(model)
+    sd = sd64(model)
     spec = orc.spec_from_model(model)
     g = torch.Generator().manual_seed(21)
     x1, x2 = (torch.randn(4, 3, 64, 64, generator=g) for _ in range(2))

@@ -13,7 +13,6 @@ the 0.5 this file asks of every case, so its two SE layers are multiplied by 8 (
 
 The kernel is checked on every shape it can run (inference.POLICY = "all", atomnas_block_infer_se_runs).
 """
-import collections
 import os
 import re
 import sys
@@ -26,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import atomnas_oracle as orc  # noqa: E402
 
-from kutil import assert_close  # noqa: E402
+from kutil import assert_close, randomize, sd64, widen_bn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BOUND = dict(rtol=1.6e-2, atol=1.6e-2, outlier_frac=0.002)
@@ -38,36 +37,6 @@ SE_SCALE = 4.0
 def _every_shape_the_kernel_runs(monkeypatch):
     import atomnas_amd.inference as inf
     monkeypatch.setattr(inf, "POLICY", "all")
-
-
-def _randomize(module, seed):   # tests/test_block_infer_gpu.py::_randomize
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:      # BN gamma
-                p.copy_(torch.rand(p.shape, generator=g) + 0.5)
-            elif p.dim() == 1:
-                p.copy_(torch.randn(p.shape, generator=g) * 0.2)
-            else:
-                fan = p[0].numel()
-                p.copy_(torch.randn(p.shape, generator=g) / fan ** 0.5)
-        for n, b in module.named_buffers():
-            if "running_mean" in n:
-                b.copy_(torch.randn(b.shape, generator=g) * 0.1)
-            elif "running_var" in n:
-                b.copy_(torch.rand(b.shape, generator=g) + 0.5)
-
-
-def _sd64(module, prefix=""):
-    return collections.OrderedDict((prefix + k, (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()))
-                                   for k, v in module.state_dict().items())
-
-
-def _widen_bn(module, factor):
-    with torch.no_grad():
-        for n, p in module.named_parameters():
-            if p.dim() == 1 and "bias" not in n:
-                p.mul_(factor)
 
 
 def _widen_se(module, factor=SE_SCALE):
@@ -109,9 +78,9 @@ def _build(cfg, stride=1):
     blk = mb.InvertedResidualChannelsFused(cfg["inp"], cfg["oup"], stride, cfg["channels"], cfg["ks"], True, active_fn=mb.get_active_fn(cfg["act"]),
                                            batch_norm_kwargs=BN_KW, se_ratio=0.5)
     blk.compute_dtype = torch.bfloat16
-    _randomize(blk, 7)
+    randomize(blk, 7)
     if cfg["act"] == "nn.ReLU6":
-        _widen_bn(blk, 4.0)
+        widen_bn(blk, 4.0)
     _widen_se(blk, cfg.get("se_scale", SE_SCALE))
     if "dbias" in cfg:
         _depthwise_bn_bias(blk, cfg["dbias"])
@@ -150,7 +119,7 @@ def _case(key):
     spec = dict(eps=1e-3, momentum=0.01, act=cfg["act"])
     ob = dict(name="blk", inp=cfg["inp"], oup=cfg["oup"], stride=1, expand=True, channels=cfg["channels"], ks=cfg["ks"],
               res=cfg["inp"] == cfg["oup"], fused=True, se=True)
-    sd = _sd64(blk, "blk.")
+    sd = sd64(blk, "blk.")
     ref, (gate,) = _oracle_gates(lambda: orc.block_forward(x.bfloat16().double(), sd, ob, False, spec, q=orc.Bf16Storage))
     span = gate.max(1).values - gate.min(1).values
     assert float(span.min()) >= 0.5, "the gates of one image hardly differ (%s): the case would not see a wrong gate" % span.tolist()
@@ -221,7 +190,7 @@ def _tiny_plus():
     from atomnas_amd.models import searched_network as sn
     model = sn.Model(num_classes=10, input_size=64, input_channel=16, last_channel=64, dropout_ratio=0.0, se_ratio=0.5, batch_norm_momentum=0.01,
                      batch_norm_epsilon=1e-3, active_fn="nn.Swish", block="InvertedResidualChannelsFused", inverted_residual_setting=ROWS)
-    _randomize(model, 5)
+    randomize(model, 5)
     _widen_se(model)
     return model
 
@@ -232,7 +201,7 @@ def test_whole_model(gpu_lib):
     bit-equal to the eager compiled model on two inputs, snapshot semantics of refresh() for the gate's tensors"""
     from atomnas_amd.inference import compile_for_inference
     model = _tiny_plus()
-    sd = _sd64(model)
+    sd = sd64(model)
     # the rows below stride the 64 x 64 input down to 4 x 4, not to the 2 x 2 that spec["pool"] = input_size // 32 assumes: the HIP tail
     # pools the whole final map (functional.tail_forward), and so does the reference here
     spec = dict(orc.spec_from_model(model), pool=4)
