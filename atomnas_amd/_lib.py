@@ -41,6 +41,11 @@ SIGNATURES = {
     "atomnas_colsum": [vp, i32, vp, i64, i32, i32, vp],
     "atomnas_fused_rmsprop_ema": [vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, i32, f64, vp, vp, vp],
     "atomnas_fused_sgd_ema": [vp, vp, vp, vp, vp, i64, vp, f64, i32, vp, vp, vp],
+    "atomnas_grad_guard": [vp, i64, vp, f32, i32, vp, vp, vp],
+    "atomnas_fused_rmsprop_ema_guarded": [vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, i32, f64, vp, vp, vp, vp],
+    "atomnas_fused_sgd_ema_guarded": [vp, vp, vp, vp, vp, i64, vp, f64, i32, vp, vp, vp, vp],
+    "atomnas_ema_update_guarded": [vp, vp, i64, vp, vp, vp],
+    "atomnas_guard_restore": [vp, vp, i64, vp, i32, vp],
     "atomnas_vec_sum": [vp, i32, f32, vp, vp],
     "atomnas_ema_update": [vp, vp, i64, vp, vp],
     "atomnas_scale_by": [vp, i64, vp, i32, vp],
@@ -70,7 +75,7 @@ SIGNATURES = {
                                i32, i32, i32, vp, vp, vp, vp, i32, i32, vp],
 }
 NO_STATUS = {"atomnas_last_error": (ctypes.c_char_p, []), "atomnas_abi_version": (i32, []),
-             "atomnas_runtime_version": (i32, []), "atomnas_expand_bwd_supported": (i32, [i32, i32, i32]),
+             "atomnas_runtime_version": (i32, []), "atomnas_grad_guard_ws_floats": (i32, []), "atomnas_expand_bwd_supported": (i32, [i32, i32, i32]),
              "atomnas_project_bwd_supported": (i32, [i32, i32, i32]),
              "atomnas_project_bwd_dp_supported": (i32, [i64, i32, i32, i32, i32, i64, i32, i64, i32, i32]),
              "atomnas_dwconv_cw_supported": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),

@@ -11,16 +11,29 @@ namespace atomnas {
 
 enum { HYP_LR = 0, HYP_RHO = 1, HYP_EMA_DECAY = 2, HYP_GRAD_SCALE = 3 };
 
+// The guard vector of a guarded step (atomnas_grad_guard writes it, the *_guarded entries read it): 8 fp32 words owned by the caller.
+//   GUARD_OK       1.0: apply the step; 0.0: the gradients are not finite and the step is dropped
+//   GUARD_SCALE    hyper[HYP_GRAD_SCALE] * coef, one fp32 product: what the guarded optimizer kernels multiply g by
+//   GUARD_NORM     sqrt(sum g^2) * hyper[HYP_GRAD_SCALE]: the L2 norm of the averaged gradient the optimizer consumes (may be Inf / NaN)
+//   GUARD_COEF     min(1, max_norm / (norm + 1e-6)), torch's clip_grad_norm_ coefficient; 1 without clipping or with a non-finite norm
+//   GUARD_SKIPPED  int32 bits: steps dropped so far       } cumulative: the kernel increments them and never clears them
+//   GUARD_CLIPPED  int32 bits: steps with coef < 1 so far }
+enum { GUARD_OK = 0, GUARD_SCALE = 1, GUARD_NORM = 2, GUARD_COEF = 3, GUARD_SKIPPED = 4, GUARD_CLIPPED = 5 };
+
 // arithmetic order follows the reference: sq.mul_(alpha).addcmul_(1-alpha, g, g); avg = sqrt(sq+eps);
 // buf.mul_(mom).addcdiv_(g, avg); p.add_(-lr, buf)
+// GUARDED: the gradient scale comes from guard[GUARD_SCALE], and with guard[GUARD_OK] == 0 nothing is written to p, sq, buf or ema (the L2
+// value, which only reads p, is still produced).  The plain instance never looks at `guard` and keeps its arithmetic and rounding order.
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void k_rmsprop_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
                                                      float* __restrict__ buf, float* __restrict__ ema,
                                                      const float* __restrict__ wd_chunk, long n, const float* __restrict__ hyper,
                                                      float alpha, float one_minus_alpha, float eps, int eps_inside_sqrt,
-                                                     float momentum, float* __restrict__ l2_part) {
+                                                     float momentum, float* __restrict__ l2_part, const float* __restrict__ guard) {
 #pragma clang fp contract(off)  // keep the reference's separate roundings (no fused multiply-add)
   __shared__ float s_part[4];
-  const float lr = hyper[HYP_LR], d = hyper[HYP_EMA_DECAY], gs = hyper[HYP_GRAD_SCALE];
+  const float lr = hyper[HYP_LR], d = hyper[HYP_EMA_DECAY], gs = GUARDED ? guard[GUARD_SCALE] : hyper[HYP_GRAD_SCALE];
+  const bool dropped = GUARDED && guard[GUARD_OK] == 0.f;
   const long nchunks = (n + 255) / 256;
   float l2acc = 0.f;
   for (long ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
@@ -29,6 +42,7 @@ __global__ __launch_bounds__(256) void k_rmsprop_ema(float* __restrict__ p, cons
     const float wd = wd_chunk ? wd_chunk[ch] : 0.f;
     float pv = p[i];
     l2acc += (wd * pv) * pv;   // value of the L2 regulariser at the weights this step's loss saw (before the update)
+    if (dropped) continue;
     float gv = g[i] * gs;
     gv = gv + wd * pv;
     float s = sq[i] * alpha;
@@ -58,13 +72,15 @@ __global__ __launch_bounds__(256) void k_rmsprop_ema(float* __restrict__ p, cons
 // d = nesterov ? g'.add(buf, alpha=momentum) : buf; p.add_(d, alpha=-lr)), with the L2 term, the 1/world scale, the EMA and the L2 value
 // exactly as in k_rmsprop_ema (same launch geometry, same summation order: the L2 value of a given arena is the same bits).
 // buf starts at zero, so the first step gives momentum * 0 + g' = g', torch's first-step `buf = g'`.
+template <bool GUARDED>   // as in k_rmsprop_ema
 __global__ __launch_bounds__(256) void k_sgd_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                  float* __restrict__ ema, const float* __restrict__ wd_chunk, long n,
                                                  const float* __restrict__ hyper, float momentum, int nesterov,
-                                                 float* __restrict__ l2_part) {
+                                                 float* __restrict__ l2_part, const float* __restrict__ guard) {
 #pragma clang fp contract(off)  // keep torch's separate roundings (no fused multiply-add)
   __shared__ float s_part[4];
-  const float lr = hyper[HYP_LR], d = hyper[HYP_EMA_DECAY], gs = hyper[HYP_GRAD_SCALE];
+  const float lr = hyper[HYP_LR], d = hyper[HYP_EMA_DECAY], gs = GUARDED ? guard[GUARD_SCALE] : hyper[HYP_GRAD_SCALE];
+  const bool dropped = GUARDED && guard[GUARD_OK] == 0.f;
   const long nchunks = (n + 255) / 256;
   float l2acc = 0.f;
   for (long ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
@@ -73,6 +89,7 @@ __global__ __launch_bounds__(256) void k_sgd_ema(float* __restrict__ p, const fl
     const float wd = wd_chunk ? wd_chunk[ch] : 0.f;
     float pv = p[i];
     l2acc += (wd * pv) * pv;   // value of the L2 regulariser at the weights this step's loss saw (before the update)
+    if (dropped) continue;
     float gv = g[i] * gs;
     gv = gv + wd * pv;
     float dv = gv;
@@ -109,9 +126,11 @@ __global__ __launch_bounds__(256) void k_sum_partials(const float* __restrict__ 
   if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + scale * s_t[0];
 }
 
+template <bool GUARDED>   // GUARDED: a no-op when guard[GUARD_OK] == 0
 __global__ __launch_bounds__(256) void k_ema(float* __restrict__ shadow, const float* __restrict__ x, long n,
-                                             const float* __restrict__ hyper) {
+                                             const float* __restrict__ hyper, const float* __restrict__ guard) {
 #pragma clang fp contract(off)
+  if (GUARDED && guard[GUARD_OK] == 0.f) return;
   const float d = hyper[HYP_EMA_DECAY];
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) shadow[i] = shadow[i] * d + (1.0f - d) * x[i];
 }
@@ -160,6 +179,87 @@ __global__ __launch_bounds__(256) void k_zero(f32x4* __restrict__ p16, long n16,
   if (blockIdx.x == 0 && (int)threadIdx.x < ntail) tail[threadIdx.x] = 0.f;
 }
 
+// ---- guarded step: global L2 norm of the gradient arena -> verdict (skip on non-finite gradients, clip_grad_norm_ coefficient)
+// Stage 1, a capped grid over the 16-byte pieces of g.  One sweep of the grid covers gridDim.x * GUARD_SWEEP pieces; in a sweep a thread
+// loads GUARD_UNROLL pieces 256 apart (all loads issued before the first use) and adds each piece's sum of squares
+// (x0^2 + x1^2) + (x2^2 + x3^2) to an accumulator of its own, so a value passes through: its square, 2 additions inside the piece, one
+// addition per sweep, 2 to join the four accumulators, [the ragged tail: 1], 6 wave levels, 3 wave partials; then stage 2.  Plain stores
+// of one partial per workgroup, no atomics: the sum does not depend on arrival order and is the same bits on every run and every rank.
+constexpr int GUARD_UNROLL = 4;
+constexpr int GUARD_SWEEP = 256 * GUARD_UNROLL;   // 16-byte pieces per workgroup and sweep
+constexpr int GUARD_MAX_BLOCKS = 1024;            // 4 workgroups per CU: 16 waves per CU with 4 KiB in flight each
+
+__global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g, long n, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float s_part[4];
+  const long n4 = n >> 2;
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  float a[GUARD_UNROLL] = {0.f, 0.f, 0.f, 0.f};
+  for (long base = (long)blockIdx.x * GUARD_SWEEP + threadIdx.x; base < n4; base += (long)gridDim.x * GUARD_SWEEP) {
+    f32x4 v[GUARD_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GUARD_UNROLL; ++u) {
+      const long i = base + u * 256;
+      v[u] = i < n4 ? g4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < GUARD_UNROLL; ++u) a[u] = a[u] + ((v[u][0] * v[u][0] + v[u][1] * v[u][1]) + (v[u][2] * v[u][2] + v[u][3] * v[u][3]));
+  }
+  float acc = (a[0] + a[1]) + (a[2] + a[3]);
+  const long t = n4 * 4 + threadIdx.x;   // ragged tail of up to 3 floats
+  if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) acc = acc + g[t] * g[t];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
+// Stage 2, one workgroup: the partials in the order of k_sum_partials, then the verdict (thread 0, plain stores).
+__global__ __launch_bounds__(256) void k_guard_verdict(const float* __restrict__ part, int nparts, const float* __restrict__ hyper,
+                                                       float max_norm, int skip_nonfinite, float* __restrict__ guard) {
+#pragma clang fp contract(off)
+  __shared__ float s_t[256];
+  float a = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
+  s_t[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_t[threadIdx.x] += s_t[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float sumsq = s_t[0], gs = hyper[HYP_GRAD_SCALE];
+    const float norm = sqrtf(sumsq) * gs;
+    const bool finite = isfinite(sumsq);   // an fp32 overflow of the sum for huge finite gradients counts as non-finite
+    float coef = 1.f;
+    if (max_norm > 0.f && isfinite(max_norm) && isfinite(norm)) {   // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+      const float c = max_norm / (norm + 1e-6f);
+      coef = c < 1.f ? c : 1.f;
+    }
+    const bool ok = finite || !skip_nonfinite;
+    guard[GUARD_OK] = ok ? 1.f : 0.f;
+    guard[GUARD_SCALE] = gs * coef;
+    guard[GUARD_NORM] = norm;
+    guard[GUARD_COEF] = coef;
+    int* cnt = reinterpret_cast<int*>(guard);
+    if (!ok) cnt[GUARD_SKIPPED] = cnt[GUARD_SKIPPED] + 1;
+    if (coef < 1.f) cnt[GUARD_CLIPPED] = cnt[GUARD_CLIPPED] + 1;
+  }
+}
+
+// dst = src over n floats when `unconditional` or guard[GUARD_OK] == 0 (the BN running statistics: their snapshot at the start of a
+// guarded step, and their way back after a dropped one).  One thread owns an element, 16-byte pieces plus a tail of up to 3 floats.
+__global__ __launch_bounds__(256) void k_guard_restore(float* __restrict__ dst, const float* __restrict__ src, long n,
+                                                       const float* __restrict__ guard, int unconditional) {
+  if (!unconditional && guard[GUARD_OK] != 0.f) return;
+  const long n4 = n >> 2;
+  f32x4* __restrict__ d4 = reinterpret_cast<f32x4*>(dst);
+  const f32x4* __restrict__ s4 = reinterpret_cast<const f32x4*>(src);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) d4[i] = s4[i];
+  const long t = n4 * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) dst[t] = src[t];
+}
+
 __global__ __launch_bounds__(256) void k_add_i64(long* __restrict__ p, long n, long v) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] += v;
 }
@@ -191,36 +291,92 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ arena, v
 
 using namespace atomnas;
 
+// the two forms of each fused optimizer entry share their checks and launch geometry; `guard` selects the kernel instance
+static int launch_rmsprop(const char* what, float* p, const float* g, float* sq, float* buf, float* ema, const float* wd_chunk, long n,
+                          const float* hyper, double alpha, double eps, int eps_inside_sqrt, double momentum, float* l2_value, float* ws,
+                          const float* guard, void* stream) {
+  ATOMNAS_REQUIRE(p && g && sq && hyper && n > 0, "%s: bad arguments", what);
+  ATOMNAS_REQUIRE(!l2_value || (ws && wd_chunk), "%s: the L2 value needs wd_chunk and a 4096-float workspace", what);
+  ATOMNAS_REQUIRE(momentum >= 0.0 && alpha >= 0.0 && eps >= 0.0, "%s: bad hyper-parameters", what);
+  ATOMNAS_REQUIRE((momentum > 0.0) == (buf != nullptr), "%s: momentum buffer must be given iff momentum > 0", what);
+  long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(guard ? k_rmsprop_ema<true> : k_rmsprop_ema<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, sq,
+                     buf, ema, wd_chunk, n, hyper, (float)alpha, (float)(1.0 - alpha), (float)eps, eps_inside_sqrt, (float)momentum,
+                     l2_value ? ws : nullptr, guard);
+  if (l2_value)
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, 1.f, 0, l2_value);
+  return check_launch(what);
+}
+
 extern "C" int atomnas_fused_rmsprop_ema(float* p, const float* g, float* sq, float* buf, float* ema, const float* wd_chunk, long n,
                                          const float* hyper, double alpha, double eps, int eps_inside_sqrt, double momentum,
                                          float* l2_value, float* ws, void* stream) {
-  ATOMNAS_REQUIRE(p && g && sq && hyper && n > 0, "fused_rmsprop_ema: bad arguments");
-  ATOMNAS_REQUIRE(!l2_value || (ws && wd_chunk), "fused_rmsprop_ema: the L2 value needs wd_chunk and a 4096-float workspace");
-  ATOMNAS_REQUIRE(momentum >= 0.0 && alpha >= 0.0 && eps >= 0.0, "fused_rmsprop_ema: bad hyper-parameters");
-  ATOMNAS_REQUIRE((momentum > 0.0) == (buf != nullptr), "fused_rmsprop_ema: momentum buffer must be given iff momentum > 0");
+  return launch_rmsprop("fused_rmsprop_ema", p, g, sq, buf, ema, wd_chunk, n, hyper, alpha, eps, eps_inside_sqrt, momentum, l2_value, ws,
+                        nullptr, stream);
+}
+
+extern "C" int atomnas_fused_rmsprop_ema_guarded(float* p, const float* g, float* sq, float* buf, float* ema, const float* wd_chunk, long n,
+                                                 const float* hyper, double alpha, double eps, int eps_inside_sqrt, double momentum,
+                                                 float* l2_value, float* ws, const float* guard, void* stream) {
+  ATOMNAS_REQUIRE(guard, "fused_rmsprop_ema_guarded: needs the guard vector");
+  return launch_rmsprop("fused_rmsprop_ema_guarded", p, g, sq, buf, ema, wd_chunk, n, hyper, alpha, eps, eps_inside_sqrt, momentum, l2_value,
+                        ws, guard, stream);
+}
+
+static int launch_sgd(const char* what, float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
+                      double momentum, int nesterov, float* l2_value, float* ws, const float* guard, void* stream) {
+  ATOMNAS_REQUIRE(p && g && hyper && n > 0, "%s: bad arguments", what);
+  ATOMNAS_REQUIRE(!l2_value || (ws && wd_chunk), "%s: the L2 value needs wd_chunk and a 4096-float workspace", what);
+  ATOMNAS_REQUIRE(momentum >= 0.0, "%s: bad hyper-parameters", what);
+  ATOMNAS_REQUIRE((momentum > 0.0) == (buf != nullptr), "%s: momentum buffer must be given iff momentum > 0", what);
+  ATOMNAS_REQUIRE(!nesterov || momentum > 0.0, "%s: Nesterov momentum needs momentum > 0", what);
   long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_rmsprop_ema, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, sq, buf, ema, wd_chunk, n, hyper,
-                     (float)alpha, (float)(1.0 - alpha), (float)eps, eps_inside_sqrt, (float)momentum, l2_value ? ws : nullptr);
+  hipLaunchKernelGGL(guard ? k_sgd_ema<true> : k_sgd_ema<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema,
+                     wd_chunk, n, hyper, (float)momentum, nesterov, l2_value ? ws : nullptr, guard);
   if (l2_value)
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, 1.f, 0, l2_value);
-  return check_launch("fused_rmsprop_ema");
+  return check_launch(what);
 }
 
 extern "C" int atomnas_fused_sgd_ema(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
                                      double momentum, int nesterov, float* l2_value, float* ws, void* stream) {
-  ATOMNAS_REQUIRE(p && g && hyper && n > 0, "fused_sgd_ema: bad arguments");
-  ATOMNAS_REQUIRE(!l2_value || (ws && wd_chunk), "fused_sgd_ema: the L2 value needs wd_chunk and a 4096-float workspace");
-  ATOMNAS_REQUIRE(momentum >= 0.0, "fused_sgd_ema: bad hyper-parameters");
-  ATOMNAS_REQUIRE((momentum > 0.0) == (buf != nullptr), "fused_sgd_ema: momentum buffer must be given iff momentum > 0");
-  ATOMNAS_REQUIRE(!nesterov || momentum > 0.0, "fused_sgd_ema: Nesterov momentum needs momentum > 0");
-  long blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_sgd_ema, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema, wd_chunk, n, hyper,
-                     (float)momentum, nesterov, l2_value ? ws : nullptr);
-  if (l2_value)
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, 1.f, 0, l2_value);
-  return check_launch("fused_sgd_ema");
+  return launch_sgd("fused_sgd_ema", p, g, buf, ema, wd_chunk, n, hyper, momentum, nesterov, l2_value, ws, nullptr, stream);
+}
+
+extern "C" int atomnas_fused_sgd_ema_guarded(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n,
+                                             const float* hyper, double momentum, int nesterov, float* l2_value, float* ws,
+                                             const float* guard, void* stream) {
+  ATOMNAS_REQUIRE(guard, "fused_sgd_ema_guarded: needs the guard vector");
+  return launch_sgd("fused_sgd_ema_guarded", p, g, buf, ema, wd_chunk, n, hyper, momentum, nesterov, l2_value, ws, guard, stream);
+}
+
+// Verdict of a guarded step from the n floats of g (16-byte aligned): guard[] as laid out next to the HYP_* enum.  ws: caller-owned
+// scratch of atomnas_grad_guard_ws_floats() floats.  Two launches, capturable, no atomics: bit-reproducible.
+extern "C" int atomnas_grad_guard_ws_floats() { return GUARD_MAX_BLOCKS; }
+
+extern "C" int atomnas_grad_guard(const float* g, long n, const float* hyper, float max_norm, int skip_nonfinite, float* ws, float* guard,
+                                  void* stream) {
+  ATOMNAS_REQUIRE(g && hyper && ws && guard && n > 0, "grad_guard: bad arguments");
+  ATOMNAS_REQUIRE(((unsigned long long)g & 15ull) == 0, "grad_guard: needs a 16-byte aligned gradient arena");
+  ATOMNAS_REQUIRE(!(max_norm != max_norm), "grad_guard: max_norm is NaN");
+  long blocks = (n / 4 + GUARD_SWEEP - 1) / GUARD_SWEEP;
+  if (blocks > GUARD_MAX_BLOCKS) blocks = GUARD_MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, ws);
+  hipLaunchKernelGGL(k_guard_verdict, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, hyper, max_norm, skip_nonfinite, guard);
+  return check_launch("grad_guard");
+}
+
+extern "C" int atomnas_guard_restore(float* dst, const float* src, long n, const float* guard, int unconditional, void* stream) {
+  ATOMNAS_REQUIRE(dst && src && n > 0 && (guard || unconditional), "guard_restore: bad arguments");
+  ATOMNAS_REQUIRE((((unsigned long long)dst | (unsigned long long)src) & 15ull) == 0, "guard_restore: needs 16-byte aligned pointers");
+  long blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_guard_restore, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dst, src, n, guard, unconditional);
+  return check_launch("guard_restore");
 }
 
 // out[0] = scale * sum_i x[i] in a fixed order (mean of the per-sample losses, train.py:178-180 `loss = torch.mean(loss)`)
@@ -234,8 +390,16 @@ extern "C" int atomnas_ema_update(float* shadow, const float* x, long n, const f
   ATOMNAS_REQUIRE(shadow && x && hyper && n > 0, "ema_update: bad arguments");
   long blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_ema, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, shadow, x, n, hyper);
+  hipLaunchKernelGGL(k_ema<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, shadow, x, n, hyper, (const float*)nullptr);
   return check_launch("ema_update");
+}
+
+extern "C" int atomnas_ema_update_guarded(float* shadow, const float* x, long n, const float* hyper, const float* guard, void* stream) {
+  ATOMNAS_REQUIRE(shadow && x && hyper && guard && n > 0, "ema_update_guarded: bad arguments");
+  long blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_ema<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, shadow, x, n, hyper, guard);
+  return check_launch("ema_update_guarded");
 }
 
 extern "C" int atomnas_scale_by(float* x, long n, const float* hyper, int idx, void* stream) {

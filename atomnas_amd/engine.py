@@ -19,6 +19,14 @@ that happens once per optimizer step.  Every micro-batch writes its gradients in
 would; one fold launch adds G to a second arena in micro-batch order, and the last fold leaves the sum in G (a second arena because
 some gradients receive two additions per backward).  The BatchNorm running statistics of every micro-batch start
 from the values at the start of the step, and the step leaves their mean.  A = 1 issues exactly what it did without the feature.
+
+Guarded step (clip_norm and / or skip_nonfinite; both off, the default: nothing of it is allocated, captured or launched).  All of it
+sits in _opt(), which every step form ends in: after the regulariser launches one fixed-order pass over the gradient arena G gives the
+global L2 norm of the averaged gradient (cross entropy + L1; the L2 term is added inside the optimizer kernel and stays outside, as a
+torch optimizer's weight_decay stays outside clip_grad_norm_), and a one-workgroup launch turns it into the verdict vector: OK, the
+gradient scale hyper[HYP_GRAD_SCALE] * clip coefficient, norm, coefficient, two cumulative counters.  The guarded optimizer launch scales
+by it, or, with OK = 0 (non-finite gradients), writes nothing; the BatchNorm running statistics, which the forward pass has already
+overwritten, then go back to their values of the start of the step, and their EMA is left alone.  Nothing synchronises with the host.
 """
 import os
 
@@ -35,10 +43,28 @@ _DEFER_REDUCE = bool(int(os.environ.get("ATOMNAS_DEFER_REDUCE", "1")))   # exper
 HYP_SUMMED_RANKS = 4   # engine-owned slot of the per-step scalar vector (runtime.ArenaManager.hyper)
 
 
+def check_clip_norm(clip_norm):
+    """TrainStep's clip_norm argument -> the maximal norm as a float, or None for no clipping (None, 0)"""
+    if clip_norm is None:
+        return None
+    if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float)):
+        raise TypeError("clip_norm must be a number or None, got %r" % (clip_norm,))
+    if not clip_norm >= 0:   # NaN included
+        raise ValueError("clip_norm must be >= 0 (0 or None: no clipping), got %r" % (clip_norm,))
+    return float(clip_norm) if clip_norm else None
+
+
 class TrainStep:
 
     def __init__(self, model, optimizer, ema=None, prune_info=None, weight_decay=1e-5, wd_method='mnas', label_smoothing=0.1,
-                 batch_size=256, image_size=224, use_graph=True, process_group=None, world_size=1, allreduce_bn=False, accum_steps=1):
+                 batch_size=256, image_size=224, use_graph=True, process_group=None, world_size=1, allreduce_bn=False, accum_steps=1,
+                 clip_norm=None, skip_nonfinite=False):
+        """clip_norm: maximal global L2 norm of the gradient the optimizer consumes (torch.nn.utils.clip_grad_norm_; None or 0: no
+        clipping).  skip_nonfinite: a step whose gradient arena holds a NaN or an Inf is dropped on the device (GradScaler-style): P, the
+        optimizer state, both EMAs and the BN running statistics keep their values of before the step.  What a dropped step still
+        advances, as GradScaler + a scheduler do: global_step, ema.note_updates (the EMA warm-up count), the learning-rate and rho
+        schedules of the caller, the dropout counter and num_batches_tracked of every BatchNorm.  guard_state() reads the verdict."""
+        self.clip_norm = check_clip_norm(clip_norm)   # first: a bad value is refused before any device work
         self.model, self.optimizer, self.ema, self.prune_info = model, optimizer, ema, prune_info
         self.weight_decay, self.wd_method = weight_decay, wd_method
         self.use_graph = use_graph
@@ -83,6 +109,14 @@ class TrainStep:
         self.g_mb = self.g_last = self.g_all_last = None   # graphs of a micro-batch / the last one / the last one with its collectives
         self._pool = None              # private pool shared by the graphs above: they never run concurrently
         self._fold_buckets = False     # the bucket hook folds its slice of G before the collective (last micro-batch, "graph" mode)
+        # guarded step
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.clip_norm is not None or self.skip_nonfinite
+        self._guard = self._guard_ws = None
+        self._sbase_version = -1
+        if self.guarded:
+            self._guard = torch.zeros(ops.GUARD_WORDS, dtype=torch.float32, device=dev)   # verdict + cumulative counters (int32 bits)
+            self._guard_ws = torch.empty(ops.grad_guard_ws_floats(), dtype=torch.float32, device=dev)
 
     # ---- pieces
     def _prune_weights(self):
@@ -195,6 +229,11 @@ class TrainStep:
         identical on every rank (train.py:171-185)."""
         mgr = self.mgr
         mgr.zero_grad()
+        if self.guarded and self.accum_steps == 1:
+            # the statistics a dropped step goes back to.  A kernel node of the captured step, not a captured copy (csrc/optim.hip k_zero
+            # records why memset-like nodes are not trusted on replay).  Accumulated steps already keep this snapshot: accumulate()
+            # takes _sbase when a group starts
+            ops.guard_restore(self._stat_base(), mgr.S, mgr.nS, None, True)
         # last False / True: a micro-batch of an accumulated step.  Its scalars were cleared when the group started (the hit counts add
         # up over the micro-batches), and the BatchNorm counters advance with the last micro-batch only
         if last is None:
@@ -222,19 +261,50 @@ class TrainStep:
             if not last:
                 ops.add_i64(mgr.step_counter, 1)   # every micro-batch draws its own dropout masks (the last one's advance is in _opt)
 
+    def _stat_base(self):
+        """buffer of S at the start of the step (guarded step, accum_steps == 1; accumulate() owns it for accumulated steps)"""
+        mgr = self.mgr
+        if self._sbase is None or self._sbase_version != mgr.version:
+            self._sbase = torch.empty(mgr.nS, dtype=torch.float32, device=mgr.P.device)
+            self._sbase_version = mgr.version
+        return self._sbase
+
     def _opt(self):
-        """[gradients summed over ranks] -> + world * rho * penalty * sign(gamma) -> the optimizer's fused launch (RMSprop or SGD) on
-        g / world + wd * p (+ EMA of the parameters, L2 value) -> L1 value -> EMA of the BN statistics."""
+        """[gradients summed over ranks] -> + world * rho * penalty * sign(gamma) -> [guarded step: verdict on G] -> the optimizer's
+        fused launch (RMSprop or SGD) on g / world + wd * p (+ EMA of the parameters, L2 value) -> L1 value -> [guarded step: S back to
+        its base after a dropped step] -> EMA of the BN statistics."""
         mgr = self.mgr
         rho_ptr = mgr.hyper[ops.HYP_RHO:ops.HYP_RHO + 1]
         if self._l1 is not None:
             table, njobs = self._l1
             ops.reg_value(mgr.P, table, njobs, 1, rho_ptr, 1.0, self.loss[2:3], ws=self._ws[4096:])
             ops.reg_grad(mgr.P, mgr.G, table, njobs, 1, rho_ptr, mgr.hyper[HYP_SUMMED_RANKS:HYP_SUMMED_RANKS + 1])
-        self.optimizer.launch_fused(mgr, mgr.EMA if self.ema is not None else None, self._wd_chunk, self.loss[1:2], self._ws)
-        if self.ema is not None:
-            ops.ema_update(mgr.SEMA, mgr.S, mgr.nS, mgr.hyper)
+        ema_arena = mgr.EMA if self.ema is not None else None
+        if not self.guarded:
+            self.optimizer.launch_fused(mgr, ema_arena, self._wd_chunk, self.loss[1:2], self._ws)
+            if self.ema is not None:
+                ops.ema_update(mgr.SEMA, mgr.S, mgr.nS, mgr.hyper)
+        else:
+            # The verdict reads G only, here: after every collective and fold, with the L1 term in.  It never reads the per-rank loss.  G
+            # is bit-identical on every rank after the all-reduce and the two launches sum in a fixed order without atomics, so every
+            # rank reaches the same verdict, scale and counters without a collective of its own (step(reduce=False) runs on one rank).
+            ops.grad_guard(mgr.G, mgr.nP, mgr.hyper, self.clip_norm or 0.0, self.skip_nonfinite, self._guard, self._guard_ws)
+            self.optimizer.launch_fused(mgr, ema_arena, self._wd_chunk, self.loss[1:2], self._ws, guard=self._guard)
+            ops.guard_restore(mgr.S, self._sbase, mgr.nS, self._guard, False)
+            if self.ema is not None:
+                ops.ema_update_guarded(mgr.SEMA, mgr.S, mgr.nS, mgr.hyper, self._guard)
         ops.add_i64(mgr.step_counter, 1)
+
+    def guard_state(self):
+        """Verdict of the last guarded step and the cumulative counters, as dict(norm=, coef=, ok=, skipped=, clipped=): norm is the
+        global L2 norm of the averaged gradient the optimizer consumed, before clipping (may be inf / nan), coef the clip coefficient.
+        Synchronises with the device when called; step() never does."""
+        if not self.guarded:
+            raise RuntimeError("guard_state(): this TrainStep was built without clip_norm and without skip_nonfinite")
+        f = self._guard.tolist()
+        c = self._guard.view(torch.int32).tolist()
+        return dict(norm=f[ops.GUARD_NORM], coef=f[ops.GUARD_COEF], ok=f[ops.GUARD_OK] != 0.0, skipped=c[ops.GUARD_SKIPPED],
+                    clipped=c[ops.GUARD_CLIPPED])
 
     def _capture(self, want_overlapped=False, accum=False):
         """accum: the graphs of an accumulated step instead (a micro-batch, the last micro-batch, the last one with its in-graph
@@ -414,7 +484,48 @@ class TrainStep:
     def step(self, lr=None, rho=0.0, ema_decay=None, reduce=None):
         """One iteration on the current static batch.  lr defaults to the optimizer's group lr.  reduce: None = all-reduce the
         gradient arena when world_size > 1; False = never (bench.py's single-rank profiling pass: the other ranks wait at a
-        barrier, so no collective may be issued)."""
+        barrier, so no collective may be issued).  A guarded step that is dropped on the device still advances everything the host
+        keeps (global_step, the EMA warm-up count) and the device counters; see __init__."""
+        do_reduce, overlapped = self._step_begin(lr, rho, ema_decay, reduce)
+        if self.accum_steps > 1:
+            self._last_micro_batch(do_reduce, overlapped)
+        else:
+            if overlapped and self.use_graph and self.g_all is None:
+                self._capture(want_overlapped=True)   # may agree on "host" over the ranks
+                overlapped = do_reduce and self.comm_mode == "graph"
+            if overlapped and self.use_graph and self.g_all is not None:
+                self.g_all.replay()
+            elif overlapped and not self.use_graph:
+                self._fwd_bwd_overlapped()
+                self._opt()
+            else:   # the step has a seam: two halves around the blocking collective (or around nothing)
+                self._half_fwd_bwd()
+                self._half_reduce(do_reduce)
+                self._half_opt()
+        self._step_end()
+
+    def _half_fwd_bwd(self):
+        if self.use_graph:
+            if self.g_fwd_bwd is None:
+                self._capture()
+            self.g_fwd_bwd.replay()
+        else:
+            self._fwd_bwd()
+
+    def _half_reduce(self, do_reduce):
+        if do_reduce:
+            dist.all_reduce(self.mgr.G, group=self.pg)
+            if self.allreduce_bn:
+                self._reduce_bn()
+
+    def _half_opt(self):
+        if self.use_graph:
+            self.g_opt.replay()
+        else:
+            self._opt()
+
+    def _step_begin(self, lr, rho, ema_decay, reduce):
+        """host side of a step before its launches: checks, comm mode, the per-step scalars -> (do_reduce, overlapped)"""
         mgr = self.mgr
         A = self.accum_steps
         if self._pending != A - 1:
@@ -446,34 +557,11 @@ class TrainStep:
         else:
             h[ops.HYP_EMA_DECAY] = -1.0
         mgr.push_hyper()
-        overlapped = do_reduce and self.comm_mode == "graph"
-        if A > 1:
-            self._last_micro_batch(do_reduce, overlapped)
-        elif self.use_graph:
-            if overlapped and self.g_all is None:
-                self._capture(want_overlapped=True)   # may agree on "host" over the ranks
-                overlapped = do_reduce and self.comm_mode == "graph"
-            if overlapped and self.g_all is not None:
-                self.g_all.replay()
-            else:
-                if self.g_fwd_bwd is None:
-                    self._capture()
-                self.g_fwd_bwd.replay()
-                if do_reduce:
-                    dist.all_reduce(mgr.G, group=self.pg)
-                    if self.allreduce_bn:
-                        self._reduce_bn()
-                self.g_opt.replay()
-        elif overlapped:
-            self._fwd_bwd_overlapped()
-            self._opt()
-        else:
-            self._fwd_bwd()
-            if do_reduce:
-                dist.all_reduce(mgr.G, group=self.pg)
-                if self.allreduce_bn:
-                    self._reduce_bn()
-            self._opt()
+        return do_reduce, do_reduce and self.comm_mode == "graph"
+
+    def _step_end(self):
+        """host bookkeeping after the launches of a step (a step dropped by the guard advances it too)"""
+        h = self.mgr.hyper_host
         # optimizer / regulariser launches outside TrainStep (RMSprop.step(), cal_bn_l1_loss) read the same vector: leave the neutral
         # scales behind (host copy only: the device vector is re-staged by whoever launches next)
         h[ops.HYP_GRAD_SCALE] = 1.0

@@ -518,18 +518,54 @@ def colsum(x, out, M, C):
     call("atomnas_colsum", _p(x), _ld(x), _p(out), M, C, dt_code(x.dtype), _stream())
 
 
-def fused_rmsprop_ema(p, g, sq, buf, ema, wd_chunk, n, hyper, alpha, eps, eps_inside_sqrt, momentum, l2_value=None, ws=None):
+def fused_rmsprop_ema(p, g, sq, buf, ema, wd_chunk, n, hyper, alpha, eps, eps_inside_sqrt, momentum, l2_value=None, ws=None, guard=None):
+    """guard (the vector grad_guard() wrote): the guarded entry -- gradient scale from guard[GUARD_SCALE], nothing written when
+    guard[GUARD_OK] == 0"""
     if l2_value is not None and ws is None:
         ws = torch.empty(4096, dtype=torch.float32, device=p.device)
-    call("atomnas_fused_rmsprop_ema", _p(p), _p(g), _p(sq), _p(buf), _p(ema), _p(wd_chunk), n, _p(hyper), float(alpha), float(eps),
-         int(eps_inside_sqrt), float(momentum), _p(l2_value), _p(ws), _stream())
+    args = (_p(p), _p(g), _p(sq), _p(buf), _p(ema), _p(wd_chunk), n, _p(hyper), float(alpha), float(eps), int(eps_inside_sqrt),
+            float(momentum), _p(l2_value), _p(ws))
+    if guard is None:
+        call("atomnas_fused_rmsprop_ema", *args, _stream())
+    else:
+        call("atomnas_fused_rmsprop_ema_guarded", *args, _p(guard), _stream())
 
 
-def fused_sgd_ema(p, g, buf, ema, wd_chunk, n, hyper, momentum, nesterov, l2_value=None, ws=None):
+def fused_sgd_ema(p, g, buf, ema, wd_chunk, n, hyper, momentum, nesterov, l2_value=None, ws=None, guard=None):
     if l2_value is not None and ws is None:
         ws = torch.empty(4096, dtype=torch.float32, device=p.device)
-    call("atomnas_fused_sgd_ema", _p(p), _p(g), _p(buf), _p(ema), _p(wd_chunk), n, _p(hyper), float(momentum), int(bool(nesterov)),
-         _p(l2_value), _p(ws), _stream())
+    args = (_p(p), _p(g), _p(buf), _p(ema), _p(wd_chunk), n, _p(hyper), float(momentum), int(bool(nesterov)), _p(l2_value), _p(ws))
+    if guard is None:
+        call("atomnas_fused_sgd_ema", *args, _stream())
+    else:
+        call("atomnas_fused_sgd_ema_guarded", *args, _p(guard), _stream())
+
+
+# ---- guarded step (engine.TrainStep(clip_norm=, skip_nonfinite=)): layout of the 8-word guard vector, include/atomnas_hip.h
+GUARD_OK, GUARD_SCALE, GUARD_NORM, GUARD_COEF, GUARD_SKIPPED, GUARD_CLIPPED = 0, 1, 2, 3, 4, 5
+GUARD_WORDS = 8
+
+
+def grad_guard_ws_floats():
+    return int(_lib.load().atomnas_grad_guard_ws_floats())
+
+
+def grad_guard(g, n, hyper, max_norm, skip_nonfinite, guard, ws=None):
+    """guard[...] = verdict on the n floats of g: global L2 norm x hyper[HYP_GRAD_SCALE], clip coefficient for max_norm (<= 0 or inf:
+    none), OK = 0 for non-finite gradients when skip_nonfinite; the two counters behind them are incremented"""
+    if ws is None:
+        ws = torch.empty(grad_guard_ws_floats(), dtype=torch.float32, device=g.device)
+    assert guard.dtype == torch.float32 and guard.numel() >= GUARD_WORDS and ws.numel() >= grad_guard_ws_floats()
+    call("atomnas_grad_guard", _p(g), int(n), _p(hyper), float(max_norm), int(bool(skip_nonfinite)), _p(ws), _p(guard), _stream())
+
+
+def ema_update_guarded(shadow, x, n, hyper, guard):
+    call("atomnas_ema_update_guarded", _p(shadow), _p(x), n, _p(hyper), _p(guard), _stream())
+
+
+def guard_restore(dst, src, n, guard, unconditional=False):
+    """dst = src over n floats when `unconditional` or guard[GUARD_OK] == 0"""
+    call("atomnas_guard_restore", _p(dst), _p(src), int(n), _p(guard), int(bool(unconditional)), _stream())
 
 
 def vec_sum(x, n, scale, out):

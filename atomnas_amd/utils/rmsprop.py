@@ -30,7 +30,8 @@ class RMSprop(ArenaOptimizer):
                         weight_decay=weight_decay)
         super().__init__(params, defaults)
 
-    def launch_fused(self, mgr, ema_arena, wd_chunk, l2_value, ws):
+    def launch_fused(self, mgr, ema_arena, wd_chunk, l2_value, ws, guard=None):
+        """guard: the verdict vector of a guarded step (engine.TrainStep): the guarded entry is launched instead"""
         group = self.param_groups[0]
         ops.fused_rmsprop_ema(mgr.P, mgr.G, mgr.SQ, mgr.BUF if group['momentum'] > 0 else None, ema_arena, wd_chunk, mgr.nP, mgr.hyper,
-                              group['alpha'], group['eps'], group['eps_inside_sqrt'], group['momentum'], l2_value=l2_value, ws=ws)
+                              group['alpha'], group['eps'], group['eps_inside_sqrt'], group['momentum'], l2_value=l2_value, ws=ws, guard=guard)

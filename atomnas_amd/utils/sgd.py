@@ -30,7 +30,8 @@ class SGD(ArenaOptimizer):
             raise NotImplementedError('weight decay enters through cal_l2_loss (utils/optim.py), as in the reference configs')
         super().__init__(params, defaults)
 
-    def launch_fused(self, mgr, ema_arena, wd_chunk, l2_value, ws):
+    def launch_fused(self, mgr, ema_arena, wd_chunk, l2_value, ws, guard=None):
+        """guard: the verdict vector of a guarded step (engine.TrainStep): the guarded entry is launched instead"""
         group = self.param_groups[0]
         ops.fused_sgd_ema(mgr.P, mgr.G, mgr.BUF if group['momentum'] > 0 else None, ema_arena, wd_chunk, mgr.nP, mgr.hyper,
-                          group['momentum'], group['nesterov'], l2_value=l2_value, ws=ws)
+                          group['momentum'], group['nesterov'], l2_value=l2_value, ws=ws, guard=guard)

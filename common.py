@@ -155,6 +155,25 @@ def grad_accum_steps():
     return int(a)
 
 
+def guard_options():
+    """the yaml's guarded-step keys -> (clip_norm or None, skip_nonfinite): grad_clip_norm (float; absent or 0: no clipping; negative:
+    ValueError) and skip_nonfinite_steps (bool, default False)"""
+    c = FLAGS.get('grad_clip_norm', None)
+    if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not c >= 0):
+        raise ValueError('grad_clip_norm must be a non-negative number (0 or absent: no clipping), got {!r}'.format(c))
+    s = FLAGS.get('skip_nonfinite_steps', False)
+    if not isinstance(s, bool):
+        raise ValueError('skip_nonfinite_steps must be true or false, got {!r}'.format(s))
+    return (float(c) if c else None), s
+
+
+def all_steps_skipped(skipped_before, skipped_now, steps):
+    """The abort rule of a guarded run: True when `steps` > 0 optimizer steps ran since the counter read `skipped_before` and every one
+    of them was dropped (the cumulative counter of engine.TrainStep.guard_state() advanced by all of them).  One dropped step among good
+    ones is what the guard is for; nothing but dropped steps is a run that has gone bad and must stop before it writes a checkpoint."""
+    return steps > 0 and skipped_now - skipped_before >= steps
+
+
 def setup_distributed(num_images=None):
     """batch_size = world * per_gpu_batch_size * grad_accum_steps; lr = base_lr * batch / base_total_batch; steps per epoch =
     ceil(N / batch) (common.py:185-209; the micro-batches of an accumulated step count as further ranks: engine.TrainStep)."""

@@ -59,6 +59,15 @@ extern "C" {
 #define ATOMNAS_HYP_EMA_DECAY 2
 #define ATOMNAS_HYP_GRAD_SCALE 3
 
+/* indices into the guard vector of a guarded step (float[8], owned by the caller; written by atomnas_grad_guard, read by the *_guarded
+ * entries and atomnas_guard_restore) */
+#define ATOMNAS_GUARD_OK 0      /* 1.0: apply the step; 0.0: non-finite gradients, the step is dropped */
+#define ATOMNAS_GUARD_SCALE 1   /* hyper[GRAD_SCALE] * coef, one fp32 product: the gradient scale of the guarded optimizer kernels */
+#define ATOMNAS_GUARD_NORM 2    /* sqrt(sum g^2) * hyper[GRAD_SCALE]: L2 norm of the averaged gradient the optimizer consumes; may be Inf / NaN */
+#define ATOMNAS_GUARD_COEF 3    /* clip coefficient min(1, max_norm / (norm + 1e-6)); 1 without clipping or with a non-finite norm */
+#define ATOMNAS_GUARD_SKIPPED 4 /* int32 bits, cumulative: steps dropped; incremented by the kernel, never cleared */
+#define ATOMNAS_GUARD_CLIPPED 5 /* int32 bits, cumulative: steps with coef < 1 */
+
 const char* atomnas_last_error(void);
 #define ATOMNAS_ABI_VERSION 9   /* 2: (ptr, ld, ss) activations, partial-row statistics, workspaces, SE / fused-backward entry points; 3: + atomnas_bnbwd_apply; 4: + atomnas_gram, atomnas_xb_coeffs, atomnas_expand_bwd with e = NULL; 5: the SE dense layers take their weights packed over the padded channel layout; 6: + atomnas_dwconv_mm_supported; 7: + atomnas_image_preprocess; 8: + atomnas_gather_jobs; 9: atomnas_expand_bwd / atomnas_project_bwd lose their two-stream forms (arguments e, c2, c3 / p, c1, c2, c3), + atomnas_fold_jobs, atomnas_image_preprocess takes the resampling filter */
 int atomnas_abi_version(void);
@@ -255,6 +264,28 @@ int atomnas_fused_rmsprop_ema(float* p, const float* g, float* sq, float* buf, f
  * Added without an ABI version change (backwards compatible). */
 int atomnas_fused_sgd_ema(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
                           double momentum, int nesterov, float* l2_value, float* ws, void* stream);
+/* ---- guarded step (added within ABI 9: new symbols, nothing existing changes)
+ * atomnas_grad_guard: sum of squares of the n floats of g (16-byte aligned) in a fixed order -- a capped grid of 16-byte loads with four
+ * accumulators per thread and a fixed tree per workgroup writes one partial per workgroup into ws (atomnas_grad_guard_ws_floats() floats,
+ * caller-owned), one workgroup sums the partials in a fixed order; no floating-point atomics, bit-reproducible -- and the verdict:
+ *   norm = sqrt(sumsq) * hyper[GRAD_SCALE];   coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch.nn.utils.clip_grad_norm_), 1 when
+ *   max_norm <= 0 or +inf (no clipping) or when the norm is not finite;   OK = skip_nonfinite ? isfinite(sumsq) : 1.
+ * A sumsq that overflows fp32 although every gradient is finite (norm beyond 1.8e19) counts as non-finite.  guard: the layout above. */
+int atomnas_grad_guard_ws_floats(void);
+int atomnas_grad_guard(const float* g, long n, const float* hyper, float max_norm, int skip_nonfinite, float* ws, float* guard, void* stream);
+/* the fused optimizer entries with the gradient scale read from guard[GUARD_SCALE] instead of hyper[GRAD_SCALE]; with guard[GUARD_OK] == 0
+ * nothing is written to p, sq, buf or ema, while l2_value (which only reads p) is still produced.  With OK = 1 and GUARD_SCALE = s they
+ * compute the bits of the plain entries run with hyper[GRAD_SCALE] = s (second instances of the same kernel bodies). */
+int atomnas_fused_rmsprop_ema_guarded(float* p, const float* g, float* sq, float* buf, float* ema, const float* wd_chunk, long n,
+                                      const float* hyper, double alpha, double eps, int eps_inside_sqrt, double momentum, float* l2_value,
+                                      float* ws, const float* guard, void* stream);
+int atomnas_fused_sgd_ema_guarded(float* p, const float* g, float* buf, float* ema, const float* wd_chunk, long n, const float* hyper,
+                                  double momentum, int nesterov, float* l2_value, float* ws, const float* guard, void* stream);
+/* atomnas_ema_update, a no-op when guard[GUARD_OK] == 0 */
+int atomnas_ema_update_guarded(float* shadow, const float* x, long n, const float* hyper, const float* guard, void* stream);
+/* dst = src over n floats (16-byte aligned pointers) when `unconditional` is set (guard may be NULL: the in-graph snapshot of the BN
+ * running statistics, a kernel node) or guard[GUARD_OK] == 0 (their restore after a dropped step); otherwise nothing is written */
+int atomnas_guard_restore(float* dst, const float* src, long n, const float* guard, int unconditional, void* stream);
 /* out[0] = scale * sum_i x[i], fixed summation order: mean of the per-sample losses (train.py:178-180) */
 int atomnas_vec_sum(const float* x, int n, float scale, float* out, void* stream);
 int atomnas_ema_update(float* shadow, const float* x, long n, const float* hyper, void* stream);

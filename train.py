@@ -275,11 +275,24 @@ def train_val_test():
     mc.profiling(model)
     FLAGS._bn_to_prune = prune.get_bn_to_prune(model, FLAGS.prune_params, verbose=udist.is_master())
     rho_scheduler = prune.get_rho_scheduler(FLAGS.prune_params, FLAGS._steps_per_epoch)
+    clip_norm, skip_nonfinite = mc.guard_options()   # a bad value stops the run here, before anything is captured
     step = engine.TrainStep(model, optimizer, ema, FLAGS._bn_to_prune, weight_decay=FLAGS.weight_decay,
                             wd_method=FLAGS.weight_decay_method, label_smoothing=FLAGS.label_smoothing,
                             batch_size=FLAGS.per_gpu_batch_size, image_size=FLAGS.image_size,
                             world_size=udist.get_world_size_fallback(),
-                            allreduce_bn=bool(FLAGS.use_distributed and FLAGS.get('allreduce_bn', False)), accum_steps=mc.grad_accum_steps())
+                            allreduce_bn=bool(FLAGS.use_distributed and FLAGS.get('allreduce_bn', False)), accum_steps=mc.grad_accum_steps(),
+                            clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
+    guard_seen = [0, FLAGS._global_step]   # the guard's skipped counter and the global step at the last check
+
+    def check_guard(where):
+        """-> guard_state().  Every optimizer step since the last check dropped: stop, before a checkpoint is written (every rank
+        reaches the same verdict, so every rank stops)"""
+        st = step.guard_state()
+        if mc.all_steps_skipped(guard_seen[0], st['skipped'], FLAGS._global_step - guard_seen[1]):
+            raise RuntimeError('step {} ({}): the gradients of every optimizer step since step {} were not finite and the steps were '
+                               'skipped; stopping before a checkpoint is written'.format(FLAGS._global_step, where, guard_seen[1]))
+        guard_seen[:] = [st['skipped'], FLAGS._global_step]
+        return st
     accum = step.accum_steps   # loader batches per optimizer step; _steps_per_epoch / max_steps_per_epoch count optimizer steps
     val_criterion = optim.CrossEntropyLabelSmooth(FLAGS.model_kwparams['num_classes'], 0.0, reduction='none')
     val_meters = mc.get_meters('val')
@@ -304,11 +317,19 @@ def train_val_test():
             step.step(lr=optimizer.param_groups[0]['lr'], rho=rho_scheduler(FLAGS._global_step))
             lr_scheduler.step()   # (allreduce_bn, when configured, happens inside the step: before the EMA, as in the reference)
             FLAGS._global_step += 1
-            if FLAGS._global_step % FLAGS.log_interval == 0 and udist.is_master():
-                ce, l2, l1 = step.loss.tolist()   # the only host synchronisation of the interval
-                dt = time.time() - t0
-                logging.info('Epoch {}/{} step {} loss {:.4f} l2 {:.4f} l1 {:.4f} lr {:.5f} {:.0f} img/s/GPU'.format(
-                    epoch, FLAGS.num_epochs, FLAGS._global_step, ce, l2, l1, optimizer.param_groups[0]['lr'], seen / dt))
+            if FLAGS._global_step % FLAGS.log_interval == 0:
+                # a guarded run reads the verdict on every rank (they all hold the same one): a run gone bad stops everywhere
+                st = check_guard('log interval') if step.guarded else None
+                if udist.is_master():
+                    ce, l2, l1 = step.loss.tolist()   # the only host synchronisation of the interval
+                    dt = time.time() - t0
+                    line = 'Epoch {}/{} step {} loss {:.4f} l2 {:.4f} l1 {:.4f} lr {:.5f} {:.0f} img/s/GPU'.format(
+                        epoch, FLAGS.num_epochs, FLAGS._global_step, ce, l2, l1, optimizer.param_groups[0]['lr'], seen / dt)
+                    if st is not None:
+                        line += ' gnorm {:.4f} skipped {} clipped {}'.format(st['norm'], st['skipped'], st['clipped'])
+                    logging.info(line)
+        if step.guarded:
+            check_guard('end of epoch {}'.format(epoch))
         results, eval_wrapper = validate(epoch, model_wrapper, ema, val_criterion, val_meters, FLAGS.get('val_steps', 4))
         if udist.is_master():
             logging.info('Epoch {} val: {}'.format(epoch, results))
