@@ -12,9 +12,13 @@ Loaders hand over decoded uint8 arrays, e.g. SyntheticDecodedImages below (bench
 (image_store.py) reads image folders that were decoded ONCE into flat uint8 shards: no decode per epoch, one staged copy per batch
 (DevicePrefetcher(staging=True)), or no pixel copy at all with the store resident in device memory (`dataset_resident: True`).
 """
+import concurrent.futures
 import ctypes
 import importlib
+import os
+import queue
 import random
+import threading
 import time
 
 import numpy as np
@@ -30,90 +34,84 @@ AUG_DTYPE = np.dtype([("oh", "<i4"), ("ow", "<i4"), ("top", "<i4"), ("left", "<i
 COLOR_OPS = {T.BRIGHTNESS: 1, T.CONTRAST: 2, T.SATURATION: 3}   # atomnas_img_aug.op
 COLOR_FORMS = {"auto": 0, "two_launch": 1, "lds": 2}            # the `form` argument of atomnas_image_color
 MAX_SCALE = 9.0   # the one-pass kernel's tap budget: a crop side above 9x the output side goes through atomnas_image_preprocess_large
-
-
 FILTERS = {"bilinear": 0, "bicubic": 1}   # the `filter` argument of atomnas_image_preprocess: PIL's BILINEAR / BICUBIC resamplers
+
+
+def _launch(entry, before, mean, std, out, out_mode, filter, after, stream):
+    """the one call behind the five wrappers below.  Every atomnas_image_* entry takes `before`, mean, std, out, out_mode, the filter
+    code (none for the colour pass), `after` and the stream, in that order; a tensor goes as its pointer, anything else as an int"""
+    arg = lambda v: ctypes.c_void_p(v.data_ptr()) if torch.is_tensor(v) else int(v)
+    m, s = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    code = () if filter is None else (FILTERS[filter],)
+    _lib.call(entry, *[arg(v) for v in before], ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), arg(out), int(out_mode),
+              *code, *[arg(v) for v in after], ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream))
 
 
 def preprocess(pool_dev, desc_dev, n, size, mean, std, out, out_mode=0, stream=None, filter="bilinear"):
     """launches atomnas_image_preprocess: pool_dev uint8 device tensor, desc_dev uint8 device tensor holding n DESC_DTYPE records"""
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-    m = (ctypes.c_float * 3)(*mean)
-    s = (ctypes.c_float * 3)(*std)
-    _lib.call("atomnas_image_preprocess", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()), int(n), int(size),
-              ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
-              ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter], st)
+    _launch("atomnas_image_preprocess", (pool_dev, desc_dev, n, size), mean, std, out, out_mode, filter, (), stream)
 
 
 def preprocess_large(pool_dev, desc_dev, sel_dev, m, max_rows, size, mean, std, out, workspace, out_mode=0, stream=None, filter="bilinear"):
     """launches atomnas_image_preprocess_large after preprocess() on the same stream: rewrites the m batch slots listed in sel_dev
     (int32 device tensor) through the two-pass form; workspace: uint8 device tensor of at least m * max_rows * size * 3 bytes"""
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-    mm = (ctypes.c_float * 3)(*mean)
-    s = (ctypes.c_float * 3)(*std)
-    _lib.call("atomnas_image_preprocess_large", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
-              ctypes.c_void_p(sel_dev.data_ptr()), int(m), int(max_rows), int(size), ctypes.cast(mm, ctypes.c_void_p),
-              ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter],
-              ctypes.c_void_p(workspace.data_ptr()), int(workspace.numel()), st)
+    _launch("atomnas_image_preprocess_large", (pool_dev, desc_dev, sel_dev, m, max_rows, size), mean, std, out, out_mode, filter,
+            (workspace, workspace.numel()), stream)
 
 
 def resize_window(pool_dev, desc_dev, aug_dev, n, size, mean, std, out, out_mode=0, stream=None, filter="bilinear"):
     """launches atomnas_image_resize_window (Resize + CenterCrop): aug_dev uint8 device tensor holding n AUG_DTYPE records"""
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-    m = (ctypes.c_float * 3)(*mean)
-    s = (ctypes.c_float * 3)(*std)
-    _lib.call("atomnas_image_resize_window", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
-              ctypes.c_void_p(aug_dev.data_ptr()), int(n), int(size), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
-              ctypes.c_void_p(out.data_ptr()), int(out_mode), FILTERS[filter], st)
+    _launch("atomnas_image_resize_window", (pool_dev, desc_dev, aug_dev, n, size), mean, std, out, out_mode, filter, (), stream)
 
 
 def resize_window_large(pool_dev, desc_dev, aug_dev, sel_dev, m, max_rows, size, mean, std, out, workspace, out_mode=0, stream=None,
                         filter="bilinear"):
     """launches atomnas_image_resize_window_large after resize_window() on the same stream (max_rows: the tallest selected IMAGE)"""
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-    mm = (ctypes.c_float * 3)(*mean)
-    s = (ctypes.c_float * 3)(*std)
-    _lib.call("atomnas_image_resize_window_large", ctypes.c_void_p(pool_dev.data_ptr()), ctypes.c_void_p(desc_dev.data_ptr()),
-              ctypes.c_void_p(aug_dev.data_ptr()), ctypes.c_void_p(sel_dev.data_ptr()), int(m), int(max_rows), int(size),
-              ctypes.cast(mm, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode),
-              FILTERS[filter], ctypes.c_void_p(workspace.data_ptr()), int(workspace.numel()), st)
+    _launch("atomnas_image_resize_window_large", (pool_dev, desc_dev, aug_dev, sel_dev, m, max_rows, size), mean, std, out, out_mode, filter,
+            (workspace, workspace.numel()), stream)
 
 
 def color(src, aug_dev, n, size, mean, std, out, means, out_mode=0, stream=None, form="auto"):
     """launches atomnas_image_color: src uint8 [n, size, size, 3] device tensor (out_mode 2 of the resize), aug_dev as above, means an
     int32 device tensor of at least n elements (scratch)"""
-    st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-    m = (ctypes.c_float * 3)(*mean)
-    s = (ctypes.c_float * 3)(*std)
     if src.numel() < n * size * size * 3 or means.numel() < n:
         raise ValueError("atomnas_image_color: source or scratch buffer too small")
-    _lib.call("atomnas_image_color", ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(aug_dev.data_ptr()), int(n), int(size),
-              ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), int(out_mode),
-              ctypes.c_void_p(means.data_ptr()), COLOR_FORMS[form], st)
+    _launch("atomnas_image_color", (src, aug_dev, n, size), mean, std, out, out_mode, None, (means, COLOR_FORMS[form]), stream)
+
+
+def _check_aug(aug, box, size):
+    """refuses the transforms.Aug that an AUG_DTYPE record cannot hold"""
+    if aug is not None and aug.ops:
+        if len(aug.ops) > 3 or sum(1 for name, _ in aug.ops if name == T.CONTRAST) > 1:
+            raise ValueError("colour decision %r: at most three ops, at most one contrast" % (aug.ops,))
+        for name, _ in aug.ops:
+            if name not in COLOR_OPS:
+                raise NotImplementedError("colour op %r (atomnas_image_color: %s)" % (name, ", ".join(COLOR_OPS)))
+    if aug is not None and aug.resize is not None:
+        oh, ow = aug.resize
+        top, left, h, w = box
+        if not (oh > 0 and ow > 0 and h == size and w == size and 0 <= top and 0 <= left and top + h <= oh and left + w <= ow):
+            raise ValueError("window %s of side %d outside a resized image of %d x %d" % (box, size, oh, ow))
 
 
 def fill_aug(rec, aug, box=None, size=None):
     """writes one AUG_DTYPE record from a transforms.Aug (None: nothing to do); `box` / `size`: the window of a resize decision"""
+    _check_aug(aug, box, size)
+    _write_aug(rec, aug, box)
+
+
+def _write_aug(rec, aug, box):   # (fill_aug behind its checks: BatchPlan.write writes what batch_plan has checked already)
     rec["op"], rec["factor"], rec["inc"] = 0, 1.0, 0.0
     rec["oh"] = rec["ow"] = rec["top"] = rec["left"] = rec["pad"] = 0
     rec["pad2"] = 0.0
     if aug is None:
         return
-    if aug.ops:
-        if len(aug.ops) > 3 or sum(1 for name, _ in aug.ops if name == T.CONTRAST) > 1:
-            raise ValueError("colour decision %r: at most three ops, at most one contrast" % (aug.ops,))
-        for k, (name, f) in enumerate(aug.ops):
-            if name not in COLOR_OPS:
-                raise NotImplementedError("colour op %r (atomnas_image_color: %s)" % (name, ", ".join(COLOR_OPS)))
-            rec["op"][k], rec["factor"][k] = COLOR_OPS[name], f
+    for k, (name, f) in enumerate(aug.ops or ()):
+        rec["op"][k], rec["factor"][k] = COLOR_OPS[name], f
     if aug.inc is not None:
         rec["inc"] = aug.inc
     if aug.resize is not None:
-        oh, ow = aug.resize
-        top, left, h, w = box
-        if not (oh > 0 and ow > 0 and h == size and w == size and 0 <= top and 0 <= left and top + h <= oh and left + w <= ow):
-            raise ValueError("window %s of side %d outside a resized image of %d x %d" % (box, size, oh, ow))
-        rec["oh"], rec["ow"], rec["top"], rec["left"] = oh, ow, top, left
+        rec["oh"], rec["ow"], rec["top"], rec["left"] = aug.resize[0], aug.resize[1], box[0], box[1]
 
 
 def check_window(H, W, resize):
@@ -130,6 +128,65 @@ def check_box(H, W, box, size):
     return h > MAX_SCALE * size or w > MAX_SCALE * size
 
 
+class BatchPlan(object):
+    """What batch_plan decides, as plain data: n; window / colour (a resize-window batch / one with a colour pass); augs (None: no aug
+    table travels); rows (staged crop-box batch: (first row, row count) per image, else None); nbytes / offs / total (the bytes of every
+    image that travel, their 16-byte-aligned pool offsets -- resident: the resident offsets -- and the pool bytes needed); large /
+    max_rows (the ordered oversize slots, the tallest in image rows (window) or box rows); entries (the launches' names in order)."""
+
+    def write(self, desc, aug, sel):
+        """fills numpy views of the tables: n DESC_DTYPE records, n AUG_DTYPE records (not read without augs), int32 slot list"""
+        for i, ((H, W), box, fl) in enumerate(zip(self.hw, self.boxes, self.flips)):
+            bi, bj, bh, bw = (0, 0, H, W) if self.window else box   # (the window mode does not read the box)
+            if self.rows is not None:   # only the box's rows travel: an image of height bh whose box starts at row 0
+                H, bi = self.rows[i][1], 0
+            desc[i] = (self.offs[i], H, W, bi, bj, bh, bw, 1 if fl else 0, 0)
+            if self.augs is not None:
+                _write_aug(aug[i], self.augs[i], box)   # (batch_plan has checked it)
+        sel[:len(self.large)] = self.large
+
+
+def batch_plan(hw, boxes, flips, augs, size, staging=False, resident_offs=None):
+    """What DevicePrefetcher does with a batch, decided from the (H, W) of its images, their boxes, flips and augs (None, or per sample
+    a transforms.Aug or None) -> BatchPlan.  Pure: no torch.cuda, no library.  Refuses a box outside its image (in a staged batch
+    before anything is sized), a batch that mixes window and crop-box samples, and what fill_aug refuses.  staging: only the rows
+    [bi, bi + bh) of a crop box travel, described as an image of height bh with bi = 0 -- k_image_preprocess and k_image_resize_h
+    (csrc/preprocess.hip) clamp their taps to the crop box, as PIL crops before it resizes, so no other row is ever read -- and whole
+    images in a window batch; resident_offs: the images are in device memory at these offsets and nothing travels."""
+    p = BatchPlan()
+    if augs is not None and all(a is None for a in augs):
+        augs = None
+    p.n, p.size, p.hw, p.boxes, p.flips, p.augs = len(hw), size, hw, boxes, flips, augs
+    p.window = augs is not None and any(a is not None and a.resize is not None for a in augs)
+    p.colour = augs is not None and any(a is not None and (a.ops or a.inc is not None) for a in augs)
+    p.rows = None
+    if resident_offs is not None:
+        p.nbytes, p.offs, p.total = [H * W * 3 for H, W in hw], list(resident_offs), 0
+    else:
+        if staging and not p.window:
+            for (H, W), box in zip(hw, boxes):
+                check_box(H, W, box, size)
+            p.rows = [(int(box[0]), int(box[2])) for box in boxes]
+        p.nbytes = [(H if p.rows is None else p.rows[i][1]) * W * 3 for i, (H, W) in enumerate(hw)]
+        p.offs, p.total = [], 0
+        for b in p.nbytes:
+            p.offs.append(p.total)
+            p.total += (b + 15) // 16 * 16
+    if p.window and not all(a is not None and a.resize is not None for a in augs):
+        raise ValueError("a batch mixes resize-window and crop-box samples")
+    p.large = []
+    for i, ((H, W), box) in enumerate(zip(hw, boxes)):
+        # (the ORIGINAL size decides, also where only the box's rows travel)
+        if check_window(H, W, augs[i].resize) if p.window else check_box(H, W, box, size):
+            p.large.append(i)
+        if augs is not None:
+            _check_aug(augs[i], box, size)
+    p.max_rows = max((hw[i][0] if p.window else int(boxes[i][2]) for i in p.large), default=0)
+    resize = "image_resize_window" if p.window else "image_preprocess"
+    p.entries = (resize,) + ((resize + "_large",) if p.large else ()) + (("image_color",) if p.colour else ())
+    return p
+
+
 class ResidentImages(object):
     """The `images` of a batch whose pixels are in device memory already (image_store.ResidentStore): `pool` the uint8 device tensor,
     `offs` the byte offset of every sample in it, `sizes` their (H, W).  DevicePrefetcher copies no pixels for such a batch."""
@@ -139,6 +196,60 @@ class ResidentImages(object):
 
     def __len__(self):
         return len(self.offs)
+
+
+class _Slot(object):
+    """One of DevicePrefetcher's two buffer sets.  Sized by ensure(): `pool` (the pixels on the device; a resident batch brings its own),
+    `desc_dev` / `desc_pin` (n DESC_DTYPE records, then the int32 batch positions of the oversize images, at most n), `out` (fp32
+    [n, 3, S, S]).  Created when a batch first needs them: `aug` (device table, pinned table, int32 scratch of the colour pass), `stage`
+    (uint8 [n, S, S, 3], the resized batch the colour pass reads), `ws` (two-pass workspace), `pin` (pinned staging buffer, staging=True).
+    The host (the worker thread), the side stream and the consumer's stream share a slot.  Who may touch it when:
+      1. The host rewrites the pinned memory -- descriptors, aug table, staging buffer -- only after wait_read().  `desc_read` is
+         recorded on the side stream behind the last host-to-device copy that reads pinned memory and in front of the launches
+         (DevicePrefetcher._queue).  Nothing else orders the host against those copies (the reference's prefetcher never reuses host
+         staging memory), and a caller that does not synchronise per step (graph replay) runs several steps ahead of the device.
+      2. The side stream waits for `consumed` before it writes the pool or the output: DevicePrefetcher.__next__ records it on the
+         consumer's stream behind the use of the slot's previous batch.
+      3. The worker acquires `free` before it submits into the slot; __next__ releases it once `consumed` is recorded."""
+
+    def __init__(self, size, max_image_bytes):
+        self.size, self.max_image_bytes, self.free = size, max_image_bytes, threading.Semaphore(1)
+        self.desc_read = self.consumed = None
+        self.drop()
+
+    def drop(self):
+        self.pool = self.desc_dev = self.desc_pin = self.out = self.aug = self.stage = self.ws = self.pin = None
+
+    def ensure(self, n, nbytes, aug, pool=True):
+        """the buffers every batch of n images and `nbytes` pool bytes needs, and the aug triple when it carries augs -> numpy views
+        of the pinned tables for BatchPlan.write: (n descriptors, n aug records or None, the int32 slot list)"""
+        if self.out is None or self.pool.numel() < nbytes or self.out.shape[0] != n:
+            cap = max(nbytes, n * self.max_image_bytes // 4) if pool else 0
+            self.pool = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            self.desc_dev = torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8, device="cuda")
+            self.desc_pin = torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8).pin_memory()
+            self.out = torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device="cuda")
+        if aug and (self.aug is None or self.aug[1].numel() < n * AUG_DTYPE.itemsize):
+            self.aug = (torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8, device="cuda"),
+                        torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.int32, device="cuda"))
+        host = self.desc_pin.numpy()
+        return (np.frombuffer(host, dtype=DESC_DTYPE, count=n), np.frombuffer(self.aug[1].numpy(), dtype=AUG_DTYPE, count=n) if aug else None,
+                np.frombuffer(host, dtype=np.int32, count=n, offset=n * DESC_DTYPE.itemsize))
+
+    def ensure_bytes(self, name, numel):
+        """the uint8 buffer `name`, allocated when it is missing or smaller than numel: 'stage' and 'ws' on the device (_queue calls
+        this under the side stream that uses them), 'pin' in pinned memory"""
+        if getattr(self, name) is None or getattr(self, name).numel() < numel:
+            buf = torch.empty(numel, dtype=torch.uint8, device="cpu" if name == "pin" else "cuda")
+            setattr(self, name, buf.pin_memory() if name == "pin" else buf)
+        return getattr(self, name)
+
+    def wait_read(self):
+        """rule 1: here is where a worker that runs ahead of the device waits for it -> the seconds that took"""
+        t = time.perf_counter()
+        if self.desc_read is not None:
+            self.desc_read.synchronize()
+        return time.perf_counter() - t
 
 
 class DevicePrefetcher(object):
@@ -151,25 +262,16 @@ class DevicePrefetcher(object):
     Aug.inc: ColorJitter's ops in their order and Lighting's increment; the batch is then resized into a per-slot uint8 staging
     buffer (allocated when the first such batch arrives) and atomnas_image_color writes the fp32 batch from it.  Aug.resize = (oh, ow):
     the whole image is resized to that and `box` is the S x S window of the RESIZED image (Resize + CenterCrop,
-    atomnas_image_resize_window); all samples of a batch or none.  The table of these decisions (atomnas_img_aug) has per-slot pinned
-    and device buffers of its own under the same reuse rule as the descriptors.  A batch of four elements, or one whose augs are all
-    None, takes exactly the launches and allocations it always took.
+    atomnas_image_resize_window); all samples of a batch or none.  A batch of four elements, or one whose augs are all None, takes
+    exactly the launches and allocations it always took.  batch_plan decides all of this per batch; _queue is what is queued, in order.
 
     The host side of a batch -- drawing it from the loader (the crop / flip decisions of 256 samples), the descriptor table, 256 copy
     submissions: ~7 ms of Python -- runs in a worker thread (threaded=True, default), one batch ahead of the hand-over; the training
-    thread only waits for an event.  Two slots (pixel pool, descriptors, output) alternate; a slot is refilled only after the consumer
-    of its previous batch has been ordered behind an event on the consumer's stream.
+    thread only waits for an event.  Two slots alternate; _Slot states what they hold and who may touch them when.
 
-    staging=True (host mode of a decoded image store, whose images are unpinned views of the page cache): the images of a batch are
-    packed into a per-slot PINNED staging buffer by `STAGE_THREADS` threads (numpy copies release the GIL) and ONE copy moves the packed
-    bytes to the device pool, instead of one pageable copy per image.  The staging buffer obeys the descriptors' rule: the host
-    rewrites it only after the slot's `desc_read` event, which is recorded behind the copy that reads it.  A crop-box batch stages only
-    the rows [bi, bi + bh) of every image and describes them as an image of height bh with bi = 0: k_image_preprocess and
-    k_image_resize_h (csrc/preprocess.hip) read the rows bi + ymin + y with ymin + y < bh -- pp_coeffs / PpWindow clamp the taps to
-    the crop box, as PIL crops before it resizes -- so no other row is ever read; whether a box is oversize is still decided on the
-    original size.  A window batch (Resize + CenterCrop reads the whole image) stages whole images.  staging=False (default) takes
-    exactly the launches, copies and allocations it always took.
-
+    staging=True (host mode of a decoded image store, whose images are unpinned views of the page cache): the images of a batch --
+    of a crop-box batch only the rows of the boxes -- are packed into the slot's PINNED staging buffer by `STAGE_THREADS` threads
+    (numpy copies release the GIL) and ONE copy moves the packed bytes to the device pool, instead of one pageable copy per image.
     Third batch form: `images` is a ResidentImages (image_store.ResidentLoader) -- the pool is the resident device tensor, desc.off the
     resident offset, and no pixel copy is issued at all; only the tables and the targets travel."""
     STAGE_THREADS = 4
@@ -183,54 +285,25 @@ class DevicePrefetcher(object):
         self.size, self.mean, self.std = int(image_size), tuple(mean), tuple(std)
         if filter not in FILTERS:
             raise NotImplementedError("resampling filter %r (atomnas_image_preprocess: %s)" % (filter, ", ".join(FILTERS)))
-        self.filter = filter
-        self.stream = torch.cuda.Stream()
-        self.device = torch.cuda.current_device()
-        self.max_image_bytes = int(max_image_bytes)
-        self.slots = [None, None]   # per slot: (device pool, device descriptors, pinned descriptors, output) sized on first use
-        self.aug = [None, None]     # per slot: (device table, pinned table, int32 scratch of the colour pass) once a batch carries augs
-        self.stage = [None, None]   # per slot: uint8 [N, S, S, 3], the resized batch the colour pass reads
-        self.ws = [None, None]      # per slot: workspace of the two-pass path, allocated when a batch first holds an oversize crop box
-        self.staging = bool(staging)
-        self.pin = [None, None]     # per slot: pinned staging buffer of the packed pixels (staging=True), under the desc_read rule
-        self._stagers = None        # thread pool of the staging copies
+        self.filter, self.stream, self.device = filter, torch.cuda.Stream(), torch.cuda.current_device()
+        self.staging = bool(staging)   # (its copies run on a thread pool: threads start when the first batch is staged)
+        self._stagers = concurrent.futures.ThreadPoolExecutor(self.STAGE_THREADS, "atomnas-stage") if self.staging else None
         # where _submit's host time went (tools/bench_feed.py): drawing the batch from the loader, waiting for the slot's desc_read event
         # (the device is behind: idle time, not work), writing the tables, packing the staging buffer, queueing copies and launches
         self.host_seconds = {"draw": 0.0, "wait": 0.0, "tables": 0.0, "stage": 0.0, "queue": 0.0}
-        # per slot: event behind the last host-to-device copy that READ the slot's pinned descriptors.  The host rewrites them for the
-        # batch after next; nothing else orders the host against that copy (the reference's prefetcher never reuses host staging
-        # memory), and a caller that does not synchronise per step (graph replay) runs several steps ahead of the device.
-        self.desc_read = [None, None]
-        self.consumed = [None, None]   # per slot: event on the consumer's stream behind the use of the slot's previous batch
-        self.k = 0                     # batches submitted
-        self._done = False             # close() has run
-        self.handed = 0                # batches handed out
-        self.threaded = bool(threaded)
+        self.k = self.handed = 0       # batches submitted (batch k goes into slot k & 1) / handed out
+        self._done, self.threaded = False, bool(threaded)   # (_done: close() has run)
+        self.slots = [_Slot(self.size, int(max_image_bytes)) for _ in range(2)]
         if self.threaded:
-            import queue
-            import threading
             self._q = queue.Queue(maxsize=1)
-            self._free = [threading.Semaphore(1), threading.Semaphore(1)]
             self._closed = False
             self._thread = threading.Thread(target=self._work, name="atomnas-prefetch", daemon=True)
             self._thread.start()
         else:
             self._pending = self._submit()
 
-    def _slot(self, q, n, nbytes, pool=True):
-        s = self.slots[q]
-        if s is None or s[0].numel() < nbytes or s[3].shape[0] != n:
-            cap = max(nbytes, n * self.max_image_bytes // 4) if pool else 0   # (a resident batch brings its pool along)
-            # descriptors, then the int32 batch positions of the oversize images (at most n)
-            s = (torch.empty(cap, dtype=torch.uint8, device="cuda"), torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8, device="cuda"),
-                 torch.empty(n * (DESC_DTYPE.itemsize + 4), dtype=torch.uint8).pin_memory(),
-                 torch.empty(n, 3, self.size, self.size, dtype=torch.float32, device="cuda"))
-            self.slots[q] = s
-        return s
-
     def _submit(self):
-        """draws the next batch and queues its copies and the preprocessing launch on the side stream -> (input, target, ready event)
-        or None at the end of the loader"""
+        """draw, plan, ensure the slot, wait for its desc_read, write, stage, queue -> (input, target, ready event); None: loader ended"""
         t0 = time.perf_counter()
         try:
             batch = next(self.loader)
@@ -238,138 +311,81 @@ class DevicePrefetcher(object):
             return None
         t1 = time.perf_counter()
         images, boxes, flips, target = batch[:4]
-        augs = batch[4] if len(batch) > 4 else None
-        if augs is not None and all(a is None for a in augs):
-            augs = None
-        q = self.k & 1
-        n = len(images)
-        window = augs is not None and any(a is not None and a.resize is not None for a in augs)
-        colour = augs is not None and any(a is not None and (a.ops or a.inc is not None) for a in augs)
         resident = isinstance(images, ResidentImages)
-        rows = None   # staged crop-box batch: (first row, row count) of every image that travels
-        if resident:
-            hw, offs = images.sizes, images.offs
-            pool, (_, desc_dev, desc_pin, out) = images.pool, self._slot(q, n, 0, pool=False)
-        else:
-            hw = [(int(im.shape[0]), int(im.shape[1])) for im in images]
-            sizes = [int(im.numel()) for im in images]
-            if self.staging and not window:
-                for (H, W), box in zip(hw, boxes):
-                    check_box(H, W, box, self.size)   # (a box outside its image is refused before it sizes anything)
-                rows = [(int(box[0]), int(box[2])) for box in boxes]
-                sizes = [bh * W * 3 for (H, W), (bi, bh) in zip(hw, rows)]
-            offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-            pool, desc_dev, desc_pin, out = self._slot(q, n, int(offs[-1]))
-        ev = self.desc_read[q]
-        tw = time.perf_counter()
-        if ev is not None:
-            # the copy queued two batches ago has read desc_pin (and the staging buffer).  A consumer that does not synchronise per step
-            # runs ahead of the device, and so does this thread: here is where it waits for the device (host_seconds['wait'])
-            ev.synchronize()
-        tw = time.perf_counter() - tw
-        d = np.frombuffer(desc_pin.numpy(), dtype=DESC_DTYPE, count=n)
-        large = []
-        if window and not all(a is not None and a.resize is not None for a in augs):
-            raise ValueError("a batch mixes resize-window and crop-box samples")
-        if augs is not None:
-            if self.aug[q] is None or self.aug[q][1].numel() < n * AUG_DTYPE.itemsize:
-                self.aug[q] = (torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8, device="cuda"),
-                               torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8).pin_memory(),
-                               torch.empty(n, dtype=torch.int32, device="cuda"))
-            aug_dev, aug_pin, means = self.aug[q]
-            a = np.frombuffer(aug_pin.numpy(), dtype=AUG_DTYPE, count=n)
-        for i, ((H, W), box, fl) in enumerate(zip(hw, boxes, flips)):
-            if window:
-                if check_window(H, W, augs[i].resize):
-                    large.append(i)
-                box_d = (0, 0, H, W)   # (not read by the window mode)
-            else:
-                if check_box(H, W, box, self.size):   # (the ORIGINAL size decides, also where only the box's rows travel)
-                    large.append(i)
-                box_d = box
-            if rows is not None:
-                H, box_d = rows[i][1], (0, box_d[1], box_d[2], box_d[3])
-            d[i] = (int(offs[i]), H, W, box_d[0], box_d[1], box_d[2], box_d[3], 1 if fl else 0, 0)
-            if augs is not None:
-                fill_aug(a[i], augs[i], box, self.size)
-        if large:
-            np.frombuffer(desc_pin.numpy(), dtype=np.int32, count=len(large), offset=n * DESC_DTYPE.itemsize)[:] = large
-            max_rows = max(hw[i][0] if window else int(boxes[i][2]) for i in large)
+        hw = images.sizes if resident else [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        plan = batch_plan(hw, boxes, flips, batch[4] if len(batch) > 4 else None, self.size, self.staging, images.offs if resident else None)
+        slot = self.slots[self.k & 1]
+        tables = slot.ensure(plan.n, plan.total, plan.augs is not None, pool=not resident)
+        tw = slot.wait_read()
+        plan.write(*tables)
         t2 = time.perf_counter()
-        staged = self.staging and not resident
-        if staged:   # behind the desc_read wait above: the copy that read this slot's staging buffer two batches ago is done
-            total = int(offs[-1])
-            pin = self._stage(q, images, rows, offs, sizes, pool.numel())
+        if self.staging and not resident:
+            self._stage(slot, images, plan)
         t3 = time.perf_counter()
-        with torch.cuda.stream(self.stream):
-            if self.consumed[q] is not None:
-                self.stream.wait_event(self.consumed[q])   # the slot's previous batch has been consumed (handed out two batches ago)
-            if staged:
-                pool[:total].copy_(pin[:total], non_blocking=True)   # in front of the desc_read event below
-            elif not resident:
-                for i, im in enumerate(images):
-                    pool[int(offs[i]):int(offs[i]) + sizes[i]].copy_(im.reshape(-1), non_blocking=True)
-            desc_dev.copy_(desc_pin, non_blocking=True)
-            if augs is not None:
-                aug_dev[:n * AUG_DTYPE.itemsize].copy_(aug_pin[:n * AUG_DTYPE.itemsize], non_blocking=True)   # in front of the event below
-            ev = self.desc_read[q] = self.desc_read[q] or torch.cuda.Event()
-            ev.record(self.stream)
-            dst, mode = out, 0
-            if colour:   # the resize writes uint8 into the staging buffer, the colour pass the batch
-                if self.stage[q] is None or self.stage[q].numel() < n * self.size * self.size * 3:
-                    self.stage[q] = torch.empty(n * self.size * self.size * 3, dtype=torch.uint8, device="cuda")
-                dst, mode = self.stage[q], 2
-            if window:
-                resize_window(pool, desc_dev, aug_dev, n, self.size, self.mean, self.std, dst, mode, self.stream, self.filter)
-            else:
-                preprocess(pool, desc_dev, n, self.size, self.mean, self.std, dst, mode, self.stream, self.filter)
-            if large:   # only batches that hold an oversize crop box pay for the second launch
-                need = len(large) * max_rows * self.size * 3
-                if self.ws[q] is None or self.ws[q].numel() < need:
-                    self.ws[q] = torch.empty(need, dtype=torch.uint8, device="cuda")   # allocated on the side stream that uses it
-                sel = desc_dev[n * DESC_DTYPE.itemsize:]
-                if window:
-                    resize_window_large(pool, desc_dev, aug_dev, sel, len(large), max_rows, self.size, self.mean, self.std, dst, self.ws[q],
-                                        mode, self.stream, self.filter)
-                else:
-                    preprocess_large(pool, desc_dev, sel, len(large), max_rows, self.size, self.mean, self.std, dst, self.ws[q], mode,
-                                     self.stream, self.filter)
-            if colour:
-                color(dst, aug_dev, n, self.size, self.mean, self.std, out, means, 0, self.stream)
-            tgt = target.cuda(non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
+        item = self._queue(plan, slot, images, target)
         self.k += 1
         hs, t4 = self.host_seconds, time.perf_counter()
         hs["draw"], hs["wait"], hs["tables"] = hs["draw"] + t1 - t0, hs["wait"] + tw, hs["tables"] + t2 - t1 - tw
         hs["stage"], hs["queue"] = hs["stage"] + t3 - t2, hs["queue"] + t4 - t3
-        return out, tgt, ready
+        return item
 
-    def _stage(self, q, images, rows, offs, sizes, capacity):
-        """packs the batch's images (`rows`: only those rows of each) into the slot's pinned staging buffer at `offs` -> the buffer"""
-        pin = self.pin[q]
-        if pin is None or pin.numel() < capacity:
-            pin = self.pin[q] = torch.empty(capacity, dtype=torch.uint8).pin_memory()
-        if self._stagers is None:
-            import concurrent.futures
-            self._stagers = concurrent.futures.ThreadPoolExecutor(max_workers=self.STAGE_THREADS, thread_name_prefix="atomnas-stage")
-        host = pin.numpy()
+    def _stage(self, slot, images, plan):
+        """packs the batch's images (plan.rows: only those rows of each) into the slot's pinned staging buffer at plan.offs"""
+        host = slot.ensure_bytes("pin", slot.pool.numel()).numpy()
 
         def copy(part):
-            for i in range(part, len(images), self.STAGE_THREADS):
+            for i in range(part, plan.n, self.STAGE_THREADS):
                 src = images[i].numpy()
-                if rows is not None:
-                    src = src[rows[i][0]:rows[i][0] + rows[i][1]]
-                np.copyto(host[int(offs[i]):int(offs[i]) + sizes[i]], src.reshape(-1))
+                if plan.rows is not None:
+                    src = src[plan.rows[i][0]:plan.rows[i][0] + plan.rows[i][1]]
+                np.copyto(host[plan.offs[i]:plan.offs[i] + plan.nbytes[i]], src.reshape(-1))
 
         list(self._stagers.map(copy, range(self.STAGE_THREADS)))   # (re-raises what a copy raised)
-        return pin
+
+    def _queue(self, plan, slot, images, target):
+        """queues a planned batch on the side stream -> (input, target, ready event).  In this order, behind the slot's `consumed`
+        event (rule 2 of _Slot): one copy per image, or the one staged copy, or none (resident); the descriptor copy; the aug copy
+        when the batch carries augs; the slot's desc_read event (rule 1: behind every copy that reads pinned memory, in front of the
+        launches); the resize; the two-pass launch when the batch has an oversize slot; the colour pass when it has one (the resize
+        then writes uint8 into slot.stage and the colour pass writes the batch); the target copy; the ready event"""
+        n, S, out = plan.n, self.size, slot.out
+        resident = isinstance(images, ResidentImages)
+        pool = images.pool if resident else slot.pool
+        with torch.cuda.stream(self.stream):
+            if slot.consumed is not None:
+                self.stream.wait_event(slot.consumed)
+            if self.staging and not resident:
+                pool[:plan.total].copy_(slot.pin[:plan.total], non_blocking=True)
+            elif not resident:
+                for im, off, nb in zip(images, plan.offs, plan.nbytes):
+                    pool[off:off + nb].copy_(im.reshape(-1), non_blocking=True)
+            slot.desc_dev.copy_(slot.desc_pin, non_blocking=True)
+            aug_dev = means = None
+            if plan.augs is not None:
+                aug_dev, aug_pin, means = slot.aug
+                aug_dev[:n * AUG_DTYPE.itemsize].copy_(aug_pin[:n * AUG_DTYPE.itemsize], non_blocking=True)
+            slot.desc_read = slot.desc_read or torch.cuda.Event()
+            slot.desc_read.record(self.stream)
+            dst, mode = (slot.ensure_bytes("stage", n * S * S * 3), 2) if plan.colour else (out, 0)
+            resize, resize_large = (resize_window, resize_window_large) if plan.window else (preprocess, preprocess_large)
+            tables = (pool, slot.desc_dev) + ((aug_dev,) if plan.window else ())
+            resize(*tables, n, S, self.mean, self.std, dst, mode, self.stream, self.filter)
+            if plan.large:   # only batches that hold an oversize crop box or image pay for the second launch
+                m, sel = len(plan.large), slot.desc_dev[n * DESC_DTYPE.itemsize:]
+                ws = slot.ensure_bytes("ws", m * plan.max_rows * S * 3)
+                resize_large(*tables, sel, m, plan.max_rows, S, self.mean, self.std, dst, ws, mode, self.stream, self.filter)
+            if plan.colour:
+                color(dst, aug_dev, n, S, self.mean, self.std, out, means, 0, self.stream)
+            tgt = target.cuda(non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+        return out, tgt, ready
 
     def _work(self):
         torch.cuda.set_device(self.device)
         try:
             while not self._closed:
-                self._free[self.k & 1].acquire()
+                self.slots[self.k & 1].free.acquire()   # (rule 3 of _Slot)
                 if self._closed:
                     break
                 item = self._submit()
@@ -382,13 +398,12 @@ class DevicePrefetcher(object):
     def __next__(self):
         cur = torch.cuda.current_stream()
         if self.handed > 0:
-            # everything the caller has queued on its stream so far -- the use of the batch handed out last time included -- is in front
-            # of this event: the slot of that batch may be refilled behind it
-            q = (self.handed - 1) & 1
-            ev = self.consumed[q] = self.consumed[q] or torch.cuda.Event()
-            ev.record(cur)
+            # (rules 2 and 3 of _Slot) everything the caller has queued so far, the use of the batch handed out last time included
+            slot = self.slots[(self.handed - 1) & 1]
+            slot.consumed = slot.consumed or torch.cuda.Event()
+            slot.consumed.record(cur)
             if self.threaded:
-                self._free[q].release()
+                slot.free.release()
         if self.threaded:
             item = self._q.get()
             if isinstance(item, BaseException):
@@ -401,13 +416,9 @@ class DevicePrefetcher(object):
         cur.wait_event(ready)
         self.handed += 1
         if not self.threaded:
-            self._pending = self._submit_after_consume()
+            # synchronous mode: the next batch goes into the OTHER slot right away, behind that slot's `consumed` of one hand-over ago
+            self._pending = self._submit()
         return out, tgt
-
-    def _submit_after_consume(self):
-        # synchronous mode: the next batch is submitted right away (it fills the OTHER slot; its own slot's consumer event, recorded
-        # one hand-over ago, is waited for on the side stream)
-        return self._submit()
 
     def close(self):
         """Safe at any point of the iteration (an evaluation that stops after `bn_calibration_steps` batches): the worker is released,
@@ -417,11 +428,9 @@ class DevicePrefetcher(object):
             return
         self._done = True
         if self.threaded:
-            import queue
-            import threading
             self._closed = True
-            for s in self._free:
-                s.release()
+            for s in self.slots:
+                s.free.release()
             if self._thread is not threading.current_thread():
                 while self._thread.is_alive():
                     try:
@@ -431,8 +440,8 @@ class DevicePrefetcher(object):
                 self._thread.join()
         self._pending = None
         self.stream.synchronize()
-        self.slots, self.ws, self.aug, self.stage = [None, None], [None, None], [None, None], [None, None]
-        self.pin = [None, None]
+        for s in self.slots:
+            s.drop()
         if self._stagers is not None:
             self._stagers.shutdown()
             self._stagers = None
@@ -450,6 +459,13 @@ class DevicePrefetcher(object):
         return self.loader_len
 
 
+def _synthetic_pool(pool_size, g, pin):
+    """`pool_size` uint8 HWC images of ImageNet-like sizes drawn in order from the generator `g`, in pinned memory when `pin`"""
+    sizes = SyntheticDecodedImages.SIZES
+    images = [torch.randint(0, 256, sizes[q % len(sizes)] + (3,), dtype=torch.uint8, generator=g) for q in range(pool_size)]
+    return [im.pin_memory() for im in images] if pin else images
+
+
 class SyntheticDecodedImages(object):
     """A stand-in for the decoded ImageNet samples of the reference's loaders (utils/dataflow.py:173-236; JPEG / LMDB are out of scope):
     `pool_size` uint8 HWC images of ImageNet-like sizes in pinned memory, batches of `batch` samples with the boxes and flips of the
@@ -461,11 +477,7 @@ class SyntheticDecodedImages(object):
     def __init__(self, batch, steps, num_classes=1000, image_size=224, pool_size=64, seed=0, train=True, transform=None):
         g = torch.Generator().manual_seed(seed)
         self.pin = torch.cuda.is_available()   # (host logic runs without a GPU)
-        self.images = []
-        for q in range(pool_size):
-            H, W = self.SIZES[q % len(self.SIZES)]
-            im = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, generator=g)
-            self.images.append(im.pin_memory() if self.pin else im)
+        self.images = _synthetic_pool(pool_size, g, self.pin)
         self.batch, self.steps, self.num_classes = batch, steps, num_classes
         self.rng_state = random.Random(seed).getstate()
         tr, va = T.mnas_bilinear_transforms(image_size)
@@ -561,15 +573,14 @@ class ColorDeviceTransform(DeviceTransform):
 def data_transforms(FLAGS):
     """Get transform of dataset (utils/dataflow.py:92-170) -> (train_transforms, val_transforms, test_transforms)."""
     name = FLAGS.data_transforms
+    size = int(FLAGS.get('image_size', 224)) if hasattr(FLAGS, 'get') else 224
     if name in ('imagenet1k_mnas_bilinear', 'imagenet1k_mnas_bicubic'):
-        size = int(FLAGS.get('image_size', 224)) if hasattr(FLAGS, 'get') else 224
         filt = name.rsplit('_', 1)[1]   # Image.BILINEAR / Image.BICUBIC of the reference: the `filter` of atomnas_image_preprocess
         (crop, flip), (vcrop, _) = T.mnas_transforms(size, filt)
         train = DeviceTransform(crop, flip, size, T.IMAGENET_MEAN, T.IMAGENET_STD, filt)
         val = DeviceTransform(vcrop, None, size, T.IMAGENET_MEAN, T.IMAGENET_STD, filt)
         return train, val, val
     if name in ('imagenet1k_inception', 'imagenet1k_mobile'):
-        size = int(FLAGS.get('image_size', 224)) if hasattr(FLAGS, 'get') else 224
         if name == 'imagenet1k_inception':
             mean, std, crop_scale = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), 0.08
         else:
@@ -614,12 +625,7 @@ class DecodedFakeData(object):
 
     def __init__(self, size, transform, num_classes=1000, pool_size=64, seed=0):
         g = torch.Generator().manual_seed(seed)
-        pin = torch.cuda.is_available()
-        self.images = []
-        for q in range(pool_size):
-            H, W = SyntheticDecodedImages.SIZES[q % len(SyntheticDecodedImages.SIZES)]
-            im = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, generator=g)
-            self.images.append(im.pin_memory() if pin else im)
+        self.images = _synthetic_pool(pool_size, g, torch.cuda.is_available())
         self.labels = torch.randint(0, num_classes, (pool_size * 16,), generator=g).tolist()
         self.size, self.transform, self.num_classes = int(size), transform, num_classes
 
@@ -647,7 +653,6 @@ class ImageFolderDecoded(object):
     split's DeviceTransform decisions: (image, box, flip[, aug], target).  The pixel work of the transform stays on the GPU."""
 
     def __init__(self, root, transform):
-        import os
         self.root, self.transform = root, transform
         classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
         if not classes:
@@ -686,21 +691,18 @@ def dataset(train_transforms, val_transforms, test_transforms, FLAGS):
     if name == 'imagenet1k_fake':
         shape = (3, FLAGS.image_size, FLAGS.image_size)
         return FakeData(size=1281167, image_size=shape, num_classes=1000), FakeData(size=50000, image_size=shape, num_classes=1000), None
+    needs_train = not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)   # (an evaluation run calibrates on the train split)
     if name == 'imagenet1k_decoded_fake':
         ntrain, nval = int(FLAGS.get('fake_train_size', 1281167)), int(FLAGS.get('fake_val_size', 50000))
         seed = int(FLAGS.get('random_seed', 0))
-        train_set = DecodedFakeData(ntrain, train_transforms, seed=seed) if (not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)) else None
+        train_set = DecodedFakeData(ntrain, train_transforms, seed=seed) if needs_train else None
         return train_set, DecodedFakeData(nval, val_transforms, seed=seed + 1), None
     if name == 'imagenet1k':
-        import os
-        train_set = (ImageFolderDecoded(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms)
-                     if (not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)) else None)
+        train_set = ImageFolderDecoded(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms) if needs_train else None
         return train_set, ImageFolderDecoded(os.path.join(FLAGS.dataset_dir, 'val'), val_transforms), None
     if name == 'imagenet1k_store':   # the image folders of 'imagenet1k', decoded once by tools/make_image_store.py
-        import os
         from .image_store import DecodedStore
-        train_set = (DecodedStore(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms)
-                     if (not FLAGS.get('test_only', False) or FLAGS.get('bn_calibration', False)) else None)
+        train_set = DecodedStore(os.path.join(FLAGS.dataset_dir, 'train'), train_transforms) if needs_train else None
         return train_set, DecodedStore(os.path.join(FLAGS.dataset_dir, 'val'), val_transforms), None
     if name == 'imagenet1k_lmdb':
         raise NotImplementedError("dataset 'imagenet1k_lmdb': the lmdb module is not in this image (utils/lmdb_dataset.py:24-71); the same "
@@ -752,7 +754,6 @@ class DecodedLoader(object):
             chunk = idx[b * self.batch_size:(b + 1) * self.batch_size]
             if self.workers > 0 and hasattr(self.dset, "load") and hasattr(self.dset, "transform"):
                 if self._pool is None:
-                    import concurrent.futures
                     self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="atomnas-decode")
                 loaded = list(self._pool.map(self.dset.load, chunk))
                 samples = []
@@ -811,6 +812,5 @@ def data_loader(train_set, val_set, test_set, FLAGS):
 
     train_loader = _build_loader(train_set, FLAGS._loader_batch_size, True) if training else None
     calib_loader = _build_loader(train_set, FLAGS.get('_loader_batch_size_calib', FLAGS._loader_batch_size), True) if calibrating else None
-    val_loader = _build_loader(val_set, FLAGS._loader_batch_size, False) if world is None else \
-        DecodedLoader(val_set, FLAGS._loader_batch_size, True, rank=rank, world=world, drop_last=FLAGS.get('drop_last', False), seed=seed, workers=workers)
+    val_loader = _build_loader(val_set, FLAGS._loader_batch_size, False)
     return train_loader, calib_loader, val_loader, val_loader

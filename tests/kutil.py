@@ -91,6 +91,52 @@ def widen_bn(module, factor):
                 p.mul_(factor)
 
 
+# ---- input-pipeline tables (tests/test_input_pipeline_gpu.py, test_preprocess_large_gpu.py, test_color_aug_gpu.py, test_image_store_gpu.py).
+# The second opinion on dataflow.batch_plan (tests/test_feed_plan.py): keep it independent of it.
+def feed_tables(images, boxes, flips, size, augs=None, base=0):
+    """What DevicePrefetcher tells the kernels about a batch of uint8 HWC images (arrays or tensors) -> (offs, desc, aug, large):
+    the 16-byte-aligned pool offsets from `base` (n + 1 of them), the DESC_DTYPE records (a batch whose augs carry a resize is a
+    window batch: its records describe whole images and `boxes` are windows of the resized ones), the AUG_DTYPE records (None
+    without augs) and the slots that need the two-pass launch.  A crop box outside its image is refused (check_box)."""
+    import numpy as np
+    from atomnas_amd.utils import dataflow as DF
+    hw = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    offs = base + np.concatenate([[0], np.cumsum([(H * W * 3 + 15) // 16 * 16 for H, W in hw])])
+    window = augs is not None and any(a is not None and a.resize is not None for a in augs)
+    desc = np.zeros(len(hw), dtype=DF.DESC_DTYPE)
+    aug = None if augs is None else np.zeros(len(hw), dtype=DF.AUG_DTYPE)
+    large = []
+    for q, ((H, W), box, fl) in enumerate(zip(hw, boxes, flips)):
+        if DF.check_window(H, W, augs[q].resize) if window else DF.check_box(H, W, box, size):
+            large.append(q)
+        desc[q] = (int(offs[q]), H, W) + ((0, 0, H, W) if window else tuple(box)) + (1 if fl else 0, 0)
+        if augs is not None:
+            DF.fill_aug(aug[q], augs[q], box, size)
+    return offs, desc, aug, large
+
+
+def feed_upload(images, boxes, flips, size, augs=None, pool=None, base=0):
+    """feed_tables on the device -> (pool, desc_dev, aug_dev, large): the images packed into `pool` (a fresh zeroed one by default)"""
+    import numpy as np
+    offs, desc, aug, large = feed_tables(images, boxes, flips, size, augs, base)
+    if pool is None:
+        pool = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda")
+    for q, im in enumerate(images):
+        flat = torch.as_tensor(im).reshape(-1)
+        pool[int(offs[q]):int(offs[q]) + flat.numel()].copy_(flat)
+    dev = lambda t: None if t is None else torch.from_numpy(t.view(np.uint8).copy()).cuda()
+    return pool, dev(desc), dev(aug), large
+
+
+def feed_out(n, size, out_mode):
+    """an output buffer of the resize / colour kernels filled with what none of them writes: fp32 NCHW (0), bf16 NHWC pitch 8 (1), uint8 (2)"""
+    if out_mode == 2:
+        return torch.full((n, size, size, 3), 77, dtype=torch.uint8, device="cuda")
+    if out_mode == 1:
+        return torch.full((n, size, size, 8), 7.0, dtype=torch.bfloat16, device="cuda")
+    return torch.full((n, 3, size, size), float("nan"), dtype=torch.float32, device="cuda")
+
+
 # ---- deterministic, RNG-free fills shared with tools/make_golden.py (inputs of the golden fixtures are regenerated, not stored)
 def counter_fill(t, seed):
     n = t.numel()

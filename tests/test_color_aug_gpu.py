@@ -17,6 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import color_ref as cr  # noqa: E402
+import kutil  # noqa: E402
 
 pr = cr.pr
 pytestmark = pytest.mark.gpu
@@ -27,33 +28,7 @@ def _fixture():
     return torch.load(os.path.join(ROOT, "tests", "golden", "color_aug.pt"), weights_only=False)
 
 
-def _upload(images, boxes, flips):
-    from atomnas_amd.utils import dataflow as DF
-    n = len(images)
-    sizes = [int(im.size) for im in images]
-    offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-    pool = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    d = np.zeros(n, dtype=DF.DESC_DTYPE)
-    for q, (im, box, fl) in enumerate(zip(images, boxes, flips)):
-        pool[int(offs[q]):int(offs[q]) + sizes[q]] = torch.from_numpy(im.reshape(-1)).cuda()
-        d[q] = (int(offs[q]), im.shape[0], im.shape[1], box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
-    return pool, torch.from_numpy(d.view(np.uint8).copy()).cuda()
-
-
-def _aug_table(augs, boxes, size):
-    from atomnas_amd.utils import dataflow as DF
-    a = np.zeros(len(augs), dtype=DF.AUG_DTYPE)
-    for q, (aug, box) in enumerate(zip(augs, boxes)):
-        DF.fill_aug(a[q], aug, box, size)
-    return torch.from_numpy(a.view(np.uint8).copy()).cuda()
-
-
-def _out(n, S, out_mode):
-    if out_mode == 2:
-        return torch.full((n, S, S, 3), 77, dtype=torch.uint8, device="cuda")
-    if out_mode == 1:
-        return torch.full((n, S, S, 8), 7.0, dtype=torch.bfloat16, device="cuda")
-    return torch.full((n, 3, S, S), float("nan"), dtype=torch.float32, device="cuda")
+_out = kutil.feed_out
 
 
 def _check_modes(u8, f32, b16, q, tag):
@@ -81,8 +56,7 @@ def test_color_pass_matches_pil_fixture_exactly(gpu_lib):
         n = len(cases)
         images = [cr.image(c["H"], c["W"], c["seed"]) for c in cases]
         boxes = [c["box"] for c in cases]
-        pool, desc = _upload(images, boxes, [c["flip"] for c in cases])
-        aug = _aug_table([T.Aug(c["ops"] or None, c["inc"], None) for c in cases], boxes, S)
+        pool, desc, aug, _ = kutil.feed_upload(images, boxes, [c["flip"] for c in cases], S, [T.Aug(c["ops"] or None, c["inc"], None) for c in cases])
         stage = _out(n, S, 2)
         DF.preprocess(pool, desc, n, S, MEAN, STD, stage, 2)
         means = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -116,8 +90,8 @@ def _window_batch(cases):
 
 def _run_window(images, boxes, flips, augs, sel, crop, mode, filt):
     from atomnas_amd.utils import dataflow as DF
-    pool, desc = _upload(images, [(0, 0, im.shape[0], im.shape[1]) for im in images], flips)
-    aug = _aug_table(augs, boxes, crop)
+    pool, desc, aug, large = kutil.feed_upload(images, boxes, flips, crop, augs)   # (a window batch: the records describe whole images)
+    assert large == sel
     o = _out(len(images), crop, mode)
     DF.resize_window(pool, desc, aug, len(images), crop, MEAN, STD, o, mode, filter=filt)
     if sel:
@@ -265,7 +239,7 @@ def test_plain_batches_allocate_nothing_new(gpu_lib):
         for q in range(5):
             e = torch.from_numpy(pr.to_tensor_normalize(pr.crop_resize_flip(imgs[q].numpy(), boxes[q], 64, flips[q]), T.IMAGENET_MEAN, T.IMAGENET_STD))
             assert torch.equal(x[q].cpu(), e)
-    assert pf.aug == [None, None] and pf.stage == [None, None] and pf.ws == [None, None]
+    assert len(pf.slots) == 2 and all(s.out is not None and s.aug is None and s.stage is None and s.ws is None for s in pf.slots)
     pf.close()
 
 

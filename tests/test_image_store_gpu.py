@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import kutil
 from test_image_store import build_both, flags  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -142,18 +143,13 @@ def test_offsets_beyond_4_gib(gpu_lib):
     n = len(images)
     far = torch.empty(5 << 30, dtype=torch.uint8, device="cuda")
     near = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
-    aug = np.zeros(n, dtype=DF.AUG_DTYPE)
+    flips = [i & 1 for i in range(n)]
+    aug = kutil.feed_tables(images, [(7, 9, S, S)] * n, flips, S, [DF.T.Aug(None, None, (2 * S, 2 * S))] * n)[2]
+    aug_dev = torch.from_numpy(aug.view(np.uint8)).cuda()
     outs = []
     for pool, base in ((near, 0), (far, (4 << 30) + 4096)):
-        desc, off = np.zeros(n, dtype=DF.DESC_DTYPE), base
-        for i, (im, box) in enumerate(zip(images, boxes)):
-            pool[off:off + im.numel()].copy_(im.reshape(-1))
-            desc[i] = (off, im.shape[0], im.shape[1]) + box + (i & 1, 0)
-            DF.fill_aug(aug[i], DF.T.Aug(None, None, (2 * S, 2 * S)), (7, 9, S, S), S)
-            off += (im.numel() + 15) // 16 * 16
-        assert base == 0 or desc["off"].min() > 1 << 32
-        desc_dev = torch.from_numpy(desc.view(np.uint8)).cuda()
-        aug_dev = torch.from_numpy(aug.view(np.uint8)).cuda()
+        _, desc_dev, _, large = kutil.feed_upload(images, boxes, flips, S, pool=pool, base=base)
+        assert large == [0] and (base == 0 or np.frombuffer(desc_dev.cpu().numpy(), dtype=DF.DESC_DTYPE)["off"].min() > 1 << 32)
         sel = torch.zeros(1, dtype=torch.int32, device="cuda")
         box_out = torch.zeros(n, 3, S, S, device="cuda")
         win_out = torch.zeros(n, 3, S, S, device="cuda")

@@ -12,6 +12,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kutil  # noqa: E402
 import pil_resize as pr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -20,21 +22,8 @@ pytestmark = pytest.mark.gpu
 def _run(images, boxes, flips, size, mean, std, out_mode, filter="bilinear"):
     from atomnas_amd.utils import dataflow as DF
     n = len(images)
-    sizes = [int(im.numel()) for im in images]
-    offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-    pool = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    d = np.zeros(n, dtype=DF.DESC_DTYPE)
-    for q, (im, box, fl) in enumerate(zip(images, boxes, flips)):
-        pool[int(offs[q]):int(offs[q]) + sizes[q]] = im.reshape(-1).cuda()
-        DF.check_box(im.shape[0], im.shape[1], box, size)
-        d[q] = (int(offs[q]), im.shape[0], im.shape[1], box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
-    desc = torch.from_numpy(d.view(np.uint8).copy()).cuda()
-    if out_mode == 2:
-        out = torch.full((n, size, size, 3), 77, dtype=torch.uint8, device="cuda")
-    elif out_mode == 1:
-        out = torch.full((n, size, size, 8), 7.0, dtype=torch.bfloat16, device="cuda")
-    else:
-        out = torch.full((n, 3, size, size), float("nan"), dtype=torch.float32, device="cuda")
+    pool, desc, _, _ = kutil.feed_upload(images, boxes, flips, size)
+    out = kutil.feed_out(n, size, out_mode)
     DF.preprocess(pool, desc, n, size, mean, std, out, out_mode, filter=filter)
     torch.cuda.synchronize()
     return out

@@ -11,6 +11,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kutil  # noqa: E402
 import pil_resize as pr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -49,23 +51,8 @@ def _launch(imgs, boxes, flips, out_mode, filt, large=True):
     """both launches the way DevicePrefetcher issues them"""
     from atomnas_amd.utils import dataflow as DF
     n = len(imgs)
-    sizes = [int(im.numel()) for im in imgs]
-    offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-    pool = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    d = np.zeros(n, dtype=DF.DESC_DTYPE)
-    sel = []
-    for q, (im, box, fl) in enumerate(zip(imgs, boxes, flips)):
-        pool[int(offs[q]):int(offs[q]) + sizes[q]] = im.reshape(-1).cuda()
-        if DF.check_box(im.shape[0], im.shape[1], box, S):
-            sel.append(q)
-        d[q] = (int(offs[q]), im.shape[0], im.shape[1], box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
-    desc = torch.from_numpy(d.view(np.uint8).copy()).cuda()
-    if out_mode == 2:
-        out = torch.full((n, S, S, 3), 77, dtype=torch.uint8, device="cuda")
-    elif out_mode == 1:
-        out = torch.full((n, S, S, 8), 7.0, dtype=torch.bfloat16, device="cuda")
-    else:
-        out = torch.full((n, 3, S, S), float("nan"), dtype=torch.float32, device="cuda")
+    pool, desc, _, sel = kutil.feed_upload(imgs, boxes, flips, S)
+    out = kutil.feed_out(n, S, out_mode)
     DF.preprocess(pool, desc, n, S, MEAN, STD, out, out_mode, filter=filt)
     if large and sel:
         rows = max(boxes[q][2] for q in sel)

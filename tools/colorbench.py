@@ -40,15 +40,12 @@ def main():
     random.seed(7)
     np.random.seed(7)
     imgs, boxes, flips, _, augs = next(iter(DF.SyntheticDecodedImages(n, 1, image_size=S, seed=7, transform=tr)))
-    sizes = [int(im.numel()) for im in imgs]
-    offs = np.concatenate([[0], np.cumsum([(b + 15) // 16 * 16 for b in sizes])])
-    pool = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    d = np.zeros(n, dtype=DF.DESC_DTYPE)
-    a = np.zeros(n, dtype=DF.AUG_DTYPE)
-    for q, (im, box, fl, aug) in enumerate(zip(imgs, boxes, flips, augs)):
-        pool[int(offs[q]):int(offs[q]) + sizes[q]] = im.reshape(-1).cuda()
-        d[q] = (int(offs[q]), im.shape[0], im.shape[1], box[0], box[1], box[2], box[3], 1 if fl else 0, 0)
-        DF.fill_aug(a[q], aug, box, S)
+    plan = DF.batch_plan([(int(im.shape[0]), int(im.shape[1])) for im in imgs], boxes, flips, augs, S)
+    pool = torch.zeros(plan.total, dtype=torch.uint8, device="cuda")
+    d, a = np.zeros(n, dtype=DF.DESC_DTYPE), np.zeros(n, dtype=DF.AUG_DTYPE)
+    plan.write(d, a, np.zeros(n, dtype=np.int32))
+    for im, off, nb in zip(imgs, plan.offs, plan.nbytes):
+        pool[off:off + nb] = im.reshape(-1).cuda()
     desc = torch.from_numpy(d.view(np.uint8).copy()).cuda()
     aug_dev = torch.from_numpy(a.view(np.uint8).copy()).cuda()
     stage = torch.empty(n, S, S, 3, dtype=torch.uint8, device="cuda")
