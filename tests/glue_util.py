@@ -138,10 +138,11 @@ def margin_pre(gen, M, C, act, amp=2.0, gap=2.0 ** -5):
     return t
 
 
-def margin_input(gen, M, C, scale, shift, act, dtype, min_gap=2.0 ** -6):
+def margin_input(gen, M, C, scale, shift, act, dtype, min_gap=2.0 ** -6, amp=2.0):
     """raw tensor z [M, C], rounded to the storage type, whose pre-activation z*scale + shift stays min_gap away from 0 and 6 in float64
-    AFTER the rounding; returns z as float64.  (Built with twice the gap; elements the rounding moved too close are pushed out again.)"""
-    pre = margin_pre(gen, M, C, act)
+    AFTER the rounding; returns z as float64.  (Built with twice the gap; elements the rounding moved too close are pushed out again.)
+    `amp`: margin_pre's spread of the pre-activations."""
+    pre = margin_pre(gen, M, C, act, amp=amp)
     z = ((pre - shift.double()) / scale.double()).to(dtype).double()
     for _ in range(4):
         p = z * scale.double() + shift.double()

@@ -40,6 +40,50 @@ def tol(dtype):
     return dict(rtol=2e-4, atol=2e-5) if dtype == torch.float32 else dict(rtol=1.2e-2, atol=1e-2)
 
 
+# ---- depthwise kernel tests (tests/test_dwconv_family_gpu.py)
+def fresh(M, C, dtype):
+    """output buffer as the allocator hands it out: padding channels zero, the valid region poisoned (unwritten elements are caught)"""
+    b = torch.zeros(M, pad8(C), dtype=dtype, device="cuda")
+    b[:, :C] = 7.0
+    return b
+
+
+def taps(w):
+    """[C, 1, k, k] -> the tap table [k*k][pad8(C)], fp32 on the GPU"""
+    C, _, k, _ = w.shape
+    t = torch.zeros(k * k, pad8(C), dtype=torch.float32, device="cuda")
+    t[:, :C] = w.reshape(C, k * k).t().float().cuda()
+    return t
+
+
+def act64(pre, mode):
+    """the C ABI's activation codes in float64: 0 none, 1 ReLU, 2 ReLU6, 3 Swish"""
+    if mode == 0:
+        return pre
+    if mode == 1:
+        return torch.relu(pre)
+    if mode == 2:
+        return torch.clamp(pre, 0.0, 6.0)
+    return pre * torch.sigmoid(pre)
+
+
+def out_hw(H, W, k, stride):
+    P = (k - 1) // 2
+    return (H + 2 * P - k) // stride + 1, (W + 2 * P - k) // stride + 1
+
+
+def family(lib, N, H, W, C, k, stride, dtype, dir, slab):
+    """The depthwise kernel family (k = 3 / 5 / 7) that atomnas_dwconv_fwd (dir 0) / atomnas_dwconv_bwd (dir 1) run for the shape, in the
+    order of csrc/dwconv.hip dw_pick: "mm" (dwconv_mm.hip, or the stride-2 forward of dwconv_mm2.hip), "cw" (dwconv_cw.hip), "tile".
+    `slab`: every activation operand slab-major and the tap table padded to whole 8-channel groups; anything else runs the tile kernels."""
+    if not slab:
+        return "tile"
+    q = (N, H, W, C, k, stride, 0 if dtype == torch.float32 else 1, dir)
+    if lib.atomnas_dwconv_mm_supported(*q) == 1:
+        return "mm"
+    return "cw" if lib.atomnas_dwconv_cw_supported(*q) == 1 else "tile"
+
+
 def assert_close(name, got, ref, rtol, atol, outlier_frac=0.0, rel_l2=None):
     """Element-wise |got-ref| <= atol + rtol*|ref|, except for at most `outlier_frac` of the elements (bf16 activations
     flip a ReLU mask for pre-activations within rounding distance of zero; such elements are individually wrong by a full

@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kutil import assert_close, cvec, from_act, pad8, rounded, to_act, tol
+from kutil import assert_close, cvec, family, from_act, pad8, rounded, to_act, tol
 
 pytestmark = pytest.mark.gpu
 
@@ -269,11 +269,14 @@ def test_gemm_tn_dma_form(gpu_lib, M, NU, NV, variant, slab):
     assert torch.equal(out2, 2 * out)
 
 
-# ---------------------------------------------------------------------------------------------- channel-pair-per-wave depthwise kernels
-# csrc/dwconv_cw.hip: stride 1, slab-major tensors, width a multiple of 7 -- the instances the hidden tensors of the expanding
-# blocks take.  Cases: several whole images per tile (7x7, 14x14; the last tile partly empty), one whole image per tile (30x14),
-# row-ring tiles (28x28, 56x56, a ragged last tile at 44x28), 3 strips per row (pitch rule for non-powers of two), channel
-# counts that leave the last slab / the last 8-channel group partly or wholly empty.
+# ---------------------------------------------------------------------------------------------- slab-major depthwise kernels
+# Stride 1, slab-major tensors, width a multiple of 7 -- the shapes the hidden tensors of the expanding blocks have.  They run the
+# channel-pair kernels of csrc/dwconv_cw.hip, EXCEPT in bf16 where the matrix-core kernels of csrc/dwconv_mm.hip come first in dw_pick
+# (default ATOMNAS_DW_MM): the forward at k = 5 / 7 on every shape but 44x28 (odd ring-tile height), the backward at k = 7 on the
+# row-ring shapes of even tile height (_cw_case_family; the tests assert it).  tests/test_dwconv_family_gpu.py runs the bf16 cw
+# instances those cases do not reach.  Cases: several whole images per tile (7x7, 14x14; the last tile partly empty), one whole image
+# per tile (30x14), row-ring tiles (28x28, 56x56, a ragged last tile at 44x28), 3 strips per row (pitch rule for non-powers of two),
+# channel counts that leave the last slab / the last 8-channel group partly or wholly empty.
 CW_SHAPES = [(10, 16, 7, 7), (3, 48, 14, 14), (2, 24, 56, 56), (5, 40, 28, 28), (2, 13, 21, 21), (1, 70, 28, 28), (2, 32, 30, 14),
              (2, 16, 44, 28), (3, 5, 14, 14)]
 
@@ -281,6 +284,20 @@ CW_SHAPES = [(10, 16, 7, 7), (3, 48, 14, 14), (2, 24, 56, 56), (5, 40, 28, 28), 
 def _cw_supported(N, H, W, C, k, dtype, direction, stride=1):
     from atomnas_amd import _lib
     return bool(_lib.load().atomnas_dwconv_cw_supported(N, H, W, C, k, stride, 0 if dtype == torch.float32 else 1, direction))
+
+
+def _cw_case_family(N, C, H, W, k, dtype, direction, stride=1):
+    """the family a case of test_dwconv_fwd_cw / test_dwconv_bwd_cw runs with the default switches"""
+    if dtype != torch.bfloat16 or stride != 1:
+        return "cw"
+    if direction == 0:
+        return "mm" if k in (5, 7) and (N, C, H, W) != (2, 16, 44, 28) else "cw"
+    return "mm" if k == 7 and (N, C, H, W) in ((2, 24, 56, 56), (5, 40, 28, 28), (1, 70, 28, 28)) else "cw"
+
+
+def _assert_cw_case_family(lib, N, C, H, W, k, dtype, direction, stride=1):
+    if os.environ.get("ATOMNAS_DW_CW") is None and os.environ.get("ATOMNAS_DW_MM") is None:
+        assert family(lib, N, H, W, C, k, stride, dtype, direction, True) == _cw_case_family(N, C, H, W, k, dtype, direction, stride)
 
 
 # stride 2 (csrc/dwconv_cw.hip k_dwb_cw2): lanes on the output grid -- whole output images per tile (14x14 -> 7x7, 28x28 -> 14x14),
@@ -296,6 +313,7 @@ def test_dwconv_fwd_cw(gpu_lib, dtype, k, N, C, H, W):
     ops = _ops()
     from atomnas_amd.ops import Slab
     assert _cw_supported(N, H, W, C, k, dtype, 0) or os.environ.get("ATOMNAS_DW_CW") is not None
+    _assert_cw_case_family(gpu_lib, N, C, H, W, k, dtype, 0)
     g = torch.Generator().manual_seed(3000 * k + C + H)
     x = torch.randn(N, C, H, W, generator=g)
     w = torch.randn(C, 1, k, k, generator=g) * 0.3
@@ -326,6 +344,7 @@ def test_dwconv_bwd_cw(gpu_lib, dtype, k, stride, N, C, H, W):
     ops = _ops()
     from atomnas_amd.ops import Slab
     assert _cw_supported(N, H, W, C, k, dtype, 1, stride) or os.environ.get("ATOMNAS_DW_CW") is not None
+    _assert_cw_case_family(gpu_lib, N, C, H, W, k, dtype, 1, stride)
     g = torch.Generator().manual_seed(4000 * k + C + H)
     x = torch.randn(N, C, H, W, generator=g)
     w = torch.randn(C, 1, k, k, generator=g) * 0.3
