@@ -67,6 +67,19 @@ def act64(pre, mode):
     return pre * torch.sigmoid(pre)
 
 
+def act_grad64(pre, mode):
+    """derivative of act64 at `pre` as the kernels define it (csrc/common.h act_pass, swish_grad): strict inequalities, so it is zero AT
+    0 and AT 6 (torch.clamp's autograd passes the gradient at its bounds)"""
+    if mode == 0:
+        return torch.ones_like(pre)
+    if mode == 1:
+        return (pre > 0).to(pre.dtype)
+    if mode == 2:
+        return ((pre > 0) & (pre < 6)).to(pre.dtype)
+    s = torch.sigmoid(pre)
+    return s * (1 + pre * (1 - s))
+
+
 def out_hw(H, W, k, stride):
     P = (k - 1) // 2
     return (H + 2 * P - k) // stride + 1, (W + 2 * P - k) // stride + 1
@@ -102,6 +115,104 @@ def assert_close(name, got, ref, rtol, atol, outlier_frac=0.0, rel_l2=None):
         raise AssertionError("%s: %d/%d mismatches, max err %.4g (ref max %.4g), first at %s got %.6g ref %.6g" %
                              (name, int(bad.sum()), bad.numel(), float(err.max()), float(ref.abs().max()), idx,
                               float(got[tuple(idx)]), float(ref[tuple(idx)])))
+
+
+# ---- Squeeze-and-Excitation kernel tests (tests/test_se_gpu.py, test_se_family_gpu.py, test_se_reference.py)
+def se_layout(widths):
+    """branch widths -> (HT, total, cmap, segments[(padded offset, real offset, width)]): every branch in a segment of whole 16-channel
+    slabs, cmap[padded channel] = column of the reference's SE weights or -1"""
+    segs, o, st = [], 0, 0
+    for h in widths:
+        segs.append((o, st, h))
+        o += (h + 15) // 16 * 16
+        st += h
+    cmap = torch.full((o,), -1, dtype=torch.int32)
+    for sg, s0, h in segs:
+        cmap[sg:sg + h] = torch.arange(s0, s0 + h, dtype=torch.int32)
+    return o, st, cmap, segs
+
+
+def se_pack(w1, w2, b2, cmap, HT):
+    """the gate's dense layers packed over the padded layout: w1p [hid][HT], w2t [hid][HT], b2p [HT], zeros on padding"""
+    hid = w1.shape[0]
+    valid = cmap >= 0
+    idx = cmap[valid].long()
+    w1p = torch.zeros(hid, HT, dtype=torch.float32)
+    w2t = torch.zeros(hid, HT, dtype=torch.float32)
+    b2p = torch.zeros(HT, dtype=torch.float32)
+    w1p[:, valid] = w1[:, idx]
+    w2t[:, valid] = w2[idx, :].t()
+    b2p[valid] = b2[idx]
+    return w1p, w2t, b2p
+
+
+def se_sequence64(c, D, dS):
+    """float64 values of the whole SE sequence (csrc/se.hip) on the REAL channels, every derivative written out (act_grad64):
+    D, dS [M, total] raw depthwise output and the gradient of S; c carries N, HW, act, se_act, sc, sh (real channels) and w1, b1, w2, b2.
+    g is the gradient with respect to the pre-activation a = D sc + sh."""
+    import types
+    N, HW = c.N, c.HW
+    w1, b1, w2, b2 = (t.double() for t in (c.w1, c.b1, c.w2, c.b2))
+    r = types.SimpleNamespace()
+    r.a = D * c.sc.double() + c.sh.double()
+    A = act64(r.a, c.act)
+    r.pooled = A.view(N, HW, -1).mean(1)
+    r.hpre = r.pooled @ w1.t() + b1
+    r.hact = act64(r.hpre, c.se_act)
+    r.gate = torch.sigmoid(r.hact @ w2.t() + b2)
+    gm = r.gate.repeat_interleave(HW, 0)
+    r.S = A * gm
+    r.dgate = (dS * A).view(N, HW, -1).sum(1)
+    r.dz2 = r.dgate * r.gate * (1 - r.gate)
+    r.dz1 = act_grad64(r.hpre, c.se_act) * (r.dz2 @ w2)
+    r.dpooled = r.dz1 @ w1
+    r.g = act_grad64(r.a, c.act) * (dS * gm + r.dpooled.repeat_interleave(HW, 0) / HW)
+    r.dw1, r.db1 = r.dz1.t() @ r.pooled, r.dz1.sum(0)
+    r.dw2, r.db2 = r.dz2.t() @ r.hact, r.dz2.sum(0)
+    return r
+
+
+def se_reference(N, HW, widths, hid, act, se_act, dtype, seed=0):
+    """Inputs and float64 results of one SE case.  Padded [M, HT] / [HT] tensors (padding zero): D, dS (float64 values exact in `dtype`),
+    scale, shift.  Real-channel tensors: w1 [hid, total], b1, w2 [total, hid], b2, the base values `base` of the four gradient
+    accumulators, and every result of se_sequence64 plus g_stored (g rounded to `dtype`) and stats = [sum g_stored, sum g_stored D].
+    The pre-activations of the block come from glue_util.margin_input (amp 2.5): none within 2^-6 of 0 (or 6 in mode 2), so no mask can
+    flip in fp32; a mode-2 case has at least 5 % of them above 6 and 5 % below 0.  With a ReLU gate the hidden pre-activations stay
+    1e-4 away from 0 (the seed is advanced until they do).  Shared between tests: never modified."""
+    import types
+    import glue_util as G
+    HT, total, cmap, segs = se_layout(widths)
+    M = N * HW
+    valid = cmap >= 0
+    idx = valid.nonzero().flatten()
+    for attempt in range(64):
+        gen = torch.Generator().manual_seed(100003 * seed + 8191 * attempt + 131 * N + 17 * HW + HT + 7 * act + 3 * se_act)
+        c = types.SimpleNamespace(N=N, HW=HW, M=M, widths=list(widths), hid=hid, act=act, se_act=se_act, dtype=dtype, HT=HT, total=total,
+                                  cmap=cmap, valid=valid, idx=idx)
+        c.sc = torch.rand(total, generator=gen) + 0.5
+        c.sh = torch.randn(total, generator=gen) * 0.3
+        z = G.margin_input(gen, M, total, c.sc, c.sh, act, dtype, amp=2.5)
+        dSr = torch.randn(M, total, generator=gen).to(dtype).double()
+        c.w1 = torch.randn(hid, total, generator=gen) / total ** 0.5
+        c.b1 = torch.randn(hid, generator=gen) * 0.1
+        c.w2 = torch.randn(total, hid, generator=gen) / hid ** 0.5
+        c.b2 = torch.randn(total, generator=gen) * 0.1
+        c.base = [torch.randn(hid * total, generator=gen), torch.randn(hid, generator=gen), torch.randn(total * hid, generator=gen),
+                  torch.randn(total, generator=gen)]
+        c.ref = se_sequence64(c, z, dSr)
+        if se_act not in (1, 2) or float(c.ref.hpre.abs().min()) >= 1e-4:
+            break
+    else:
+        raise AssertionError("no seed keeps the hidden pre-activations away from 0")
+    if act == 2:
+        assert float((c.ref.a > 6).double().mean()) >= 0.05 and float((c.ref.a < 0).double().mean()) >= 0.05, "ReLU6 range not straddled"
+    c.D, c.dS = torch.zeros(M, HT, dtype=torch.float64), torch.zeros(M, HT, dtype=torch.float64)
+    c.D[:, idx], c.dS[:, idx] = z, dSr
+    c.scale, c.shift = torch.zeros(HT), torch.zeros(HT)
+    c.scale[idx], c.shift[idx] = c.sc, c.sh
+    c.ref.g_stored = c.ref.g.to(dtype).double()
+    c.ref.stats = torch.stack([c.ref.g_stored.sum(0), (c.ref.g_stored * z).sum(0)])
+    return c
 
 
 # ---- module-level parity tests (tests/test_block_gpu.py, tests/test_block_infer_gpu.py, tests/test_block_infer_se_gpu.py)

@@ -5,37 +5,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kutil import assert_close
+from kutil import assert_close, se_layout as _layout, se_pack as _pack
 
 pytestmark = pytest.mark.gpu
 
 ACT_RELU, ACT_SWISH = 1, 3
-
-
-def _layout(hid_list):
-    """branch widths -> (HT, total, cmap, segments[(padded offset, real offset, width)])"""
-    segs, o, st = [], 0, 0
-    for h in hid_list:
-        segs.append((o, st, h))
-        o += (h + 15) // 16 * 16
-        st += h
-    cmap = torch.full((o,), -1, dtype=torch.int32)
-    for sg, s0, h in segs:
-        cmap[sg:sg + h] = torch.arange(s0, s0 + h, dtype=torch.int32)
-    return o, st, cmap, segs
-
-
-def _pack(w1, w2, b2, cmap, HT):
-    hid = w1.shape[0]
-    valid = cmap >= 0
-    idx = cmap[valid].long()
-    w1p = torch.zeros(hid, HT, dtype=torch.float32)
-    w2t = torch.zeros(hid, HT, dtype=torch.float32)
-    b2p = torch.zeros(HT, dtype=torch.float32)
-    w1p[:, valid] = w1[:, idx]
-    w2t[:, valid] = w2[idx, :].t()
-    b2p[valid] = b2[idx]
-    return w1p, w2t, b2p
 
 
 def _act(x, code):
