@@ -42,6 +42,9 @@ def model_kwparams(name):
                 batch_norm_momentum=0.01, batch_norm_epsilon=1e-3)
     if name == 'atomnas_c_supernet':
         return dict(base, input_channel=32, inverted_residual_setting=[list(r) for r in _SUPERNET_ROWS])
+    if name == 'atomnas_c_se_supernet':   # apps/slimming/shrink/atomnas_c_se.yml: the "+" search space (fused blocks, SE, Swish)
+        return dict(base, input_channel=32, inverted_residual_setting=[list(r) for r in _SUPERNET_ROWS], active_fn='nn.Swish',
+                    block='InvertedResidualChannelsFused', se_ratio=0.25)
     if name == 'atomnas_a_supernet':
         return dict(base, input_channel=16, inverted_residual_setting=[list(r) for r in _SUPERNET_ROWS])
     if name == 'atomnas_mix_supernet':

@@ -7,6 +7,7 @@ the EMA and the PruneInfo in the reference's order (shared pw_bn -> kept branche
 swapped.  The data movement behind `mask_hook` is the index-packed channel gather of libatomnas_hip.so
 (atomnas_mask_index + atomnas_gather_dim) -- there is no host copy of the weights.  After a shrink the arenas of the owning
 model are rebuilt lazily (runtime.ArenaManager.materialize) at the next forward / optimizer step.
+`compress_inverted_residual_channels_fused` is the same protocol for InvertedResidualChannelsFused, which the reference cannot shrink.
 """
 import functools
 import itertools
@@ -70,27 +71,27 @@ def build_default_info(m_new, m_old, mask, attr, mask_hook, var_type='variable',
     return info
 
 
-def compress_conv(m_new, m_old, mask, dim, prefix_new=None, prefix_old=None):
+def compress_conv(m_new, m_old, mask, dim, prefix_new=None, prefix_old=None, gather=_mask_along_dim):
     assert m_new is None or isinstance(m_new, nn.Conv2d)
     assert isinstance(m_old, nn.Conv2d) and dim in (0, 1)
     mk = functools.partial(build_default_info, m_new, m_old, mask, prefix_new=prefix_new, prefix_old=prefix_old)
-    infos = [mk('weight', functools.partial(_mask_along_dim, dim=dim))]
+    infos = [mk('weight', functools.partial(gather, dim=dim))]
     if m_old.bias is not None:
-        infos.append(mk('bias', _mask_along_dim if dim == 0 else _copy))
+        infos.append(mk('bias', gather if dim == 0 else _copy))
     return infos
 
 
-def compress_bn(m_new, m_old, mask, prefix_new=None, prefix_old=None):
+def compress_bn(m_new, m_old, mask, prefix_new=None, prefix_old=None, gather=_mask_along_dim):
     assert m_new is None or isinstance(m_new, nn.BatchNorm2d)
     assert isinstance(m_old, nn.BatchNorm2d)
     assert m_new is None or m_new.affine == m_old.affine
     infos = []
     if m_old.affine:
         mk = functools.partial(build_default_info, m_new, m_old, mask, prefix_new=prefix_new, prefix_old=prefix_old)
-        infos += [mk('weight', _mask_along_dim), mk('bias', _mask_along_dim)]
+        infos += [mk('weight', gather), mk('bias', gather)]
     if m_old.track_running_stats:
         mkb = functools.partial(build_default_info, m_new, m_old, mask, var_type='buffer', prefix_new=prefix_new, prefix_old=prefix_old)
-        infos += [mkb('running_var', _mask_along_dim), mkb('running_mean', _mask_along_dim), mkb('num_batches_tracked', _copy)]
+        infos += [mkb('running_var', gather), mkb('running_mean', gather), mkb('num_batches_tracked', _copy)]
     return infos
 
 
@@ -107,17 +108,19 @@ def adjust_bn(m_new, m_old, post_hook_params, **kwargs):
     return infos
 
 
-def compress_conv_bn_relu(m_new, m_old, mask, prefix_new=None, prefix_old=None, dim=0):
+def compress_conv_bn_relu(m_new, m_old, mask, prefix_new=None, prefix_old=None, dim=0, gather=_mask_along_dim):
     from . import mobilenet_base as mb
     assert m_new is None or isinstance(m_new, mb.ConvBNReLU)
     assert isinstance(m_old, mb.ConvBNReLU)
     old = list(m_old.children())
     new = [None] * len(old) if m_new is None else list(m_new.children())
-    return (compress_conv(new[0], old[0], mask, dim=dim, prefix_new='{}.0'.format(prefix_new), prefix_old='{}.0'.format(prefix_old)) +
-            compress_bn(new[1], old[1], mask, prefix_new='{}.1'.format(prefix_new), prefix_old='{}.1'.format(prefix_old)))
+    return (compress_conv(new[0], old[0], mask, dim=dim, prefix_new='{}.0'.format(prefix_new), prefix_old='{}.0'.format(prefix_old),
+                          gather=gather) +
+            compress_bn(new[1], old[1], mask, prefix_new='{}.1'.format(prefix_new), prefix_old='{}.1'.format(prefix_old), gather=gather))
 
 
-def copmress_inverted_residual_channels(m, masks, ema=None, optimizer=None, prune_info=None, prefix=None, verbose=False):
+def _protocol(ema, optimizer, prune_info, verbose):
+    """(update, clean) of one block's shrink: what happens to a kept / a dropped tensor in the optimizer, the EMA and the PruneInfo."""
     def is_prunable_bn_var(info):
         return prune_info is not None and issubclass(info['module_class'], nn.BatchNorm2d) and info['type'] == 'variable'
 
@@ -142,6 +145,19 @@ def copmress_inverted_residual_channels(m, masks, ema=None, optimizer=None, prun
             if is_prunable_bn_var(info) and prune_info.compress_check_exist(info):
                 prune_info.compress_drop(info, verbose=verbose)
 
+    return update, clean
+
+
+def _swap_done(m):
+    """the structure changed: the arenas of the owning model are rebuilt at the next use"""
+    pl = getattr(m, '_plan', None)
+    if pl is not None and getattr(pl, 'mgr', None) is not None:
+        pl.mgr.mark_dirty()
+    object.__setattr__(m, '_plan', None)
+
+
+def copmress_inverted_residual_channels(m, masks, ema=None, optimizer=None, prune_info=None, prefix=None, verbose=False):
+    update, clean = _protocol(ema, optimizer, prune_info, verbose)
     assert len(m.kernel_sizes) == len(masks)
     device = m.pw_bn.weight.device
     hidden = [ops.mask_count(mask) for mask in masks]   # from the shrink's one mask launch when it registered them, else mask.sum().item()
@@ -185,8 +201,91 @@ def copmress_inverted_residual_channels(m, masks, ema=None, optimizer=None, prun
     del m.ops
     del m.pw_bn
     m.ops, m.pw_bn = new_ops, new_pw_bn
-    # the structure changed: the arenas of the owning model are rebuilt at the next use
-    pl = getattr(m, '_plan', None)
-    if pl is not None and getattr(pl, 'mgr', None) is not None:
-        pl.mgr.mark_dirty()
-    object.__setattr__(m, '_plan', None)
+    _swap_done(m)
+
+
+def _mask_segments(lhs, rhs, segs, dim=0):
+    """The fused block's concatenated mask (the per-branch masks in branch order) as one gather per kept branch slice, on views:
+    lhs[new_start : new_start + kept] <- rhs[start : start + hidden][mask] along `dim` for every segment of `segs`."""
+    if dim not in (0, 1):
+        raise NotImplementedError()
+    for mask, start, hidden, new_start, kept in segs:
+        ops.gather_by_mask(lhs.data.narrow(dim, new_start, kept), rhs.data.narrow(dim, start, hidden), mask, dim)
+
+
+def compress_inverted_residual_channels_fused(m, masks, ema=None, optimizer=None, prune_info=None, prefix=None, verbose=False):
+    """The shrink of an expanding InvertedResidualChannelsFused, with the protocol of the plain block.  Its expand conv, SE gate and
+    projection span all hidden channels: they are gathered with the concatenated mask (_mask_segments); the depthwise branches with their
+    own.  A branch without a live atom is dropped and the remaining ones renumbered; a block without a live atom becomes the identity and
+    every tensor of it is dropped."""
+    from . import mobilenet_base as mb
+    if not m.expand:
+        raise RuntimeError('Not search_first')
+    update, clean = _protocol(ema, optimizer, prune_info, verbose)
+    assert len(m.kernel_sizes) == len(masks) == len(m.depth_ops)
+    old_project = m.project_conv
+    device = old_project[0].weight.device
+    old_hidden = list(m.channels)
+    hidden = [ops.mask_count(mask) for mask in masks]
+    keeps = [h > 0 for h in hidden]
+    segs, start, new_start = [], 0, 0
+    for mask, h_old, h_new in zip(masks, old_hidden, hidden):
+        assert mask.numel() == h_old
+        if h_new > 0:
+            segs.append((mask, start, h_old, new_start, h_new))
+        start += h_old
+        new_start += h_new
+    m.channels, m.kernel_sizes = [list(itertools.compress(x, keeps)) for x in (hidden, m.kernel_sizes)]
+    with _build_on(device):
+        new_expand, new_depth, new_project, new_se = m._build(m.channels, m.kernel_sizes, m.expand, m.se_ratio)
+    for top in (new_expand, new_depth, new_project, new_se):   # train / eval state follows the block
+        for mod in top.modules():
+            mod.training = m.training
+    alive = len(new_depth) > 0
+    has_se = isinstance(m.se_op, mb.SqueezeAndExcitation)
+    name = functools.partial(add_prefix, prefix=prefix)
+
+    # tensors over all hidden channels: the concatenated mask; None for the new module when the block dies
+    wide = functools.partial(dict, gather=_mask_segments)
+    shared = compress_conv_bn_relu(new_expand if alive else None, m.expand_conv, segs, name('expand_conv'), name('expand_conv'), **wide())
+    if has_se:
+        new_r, new_e = (new_se.se_reduce, new_se.se_expand) if alive else (None, None)
+        shared += compress_conv(new_r, m.se_op.se_reduce, segs, dim=1, prefix_new=name('se_op.se_reduce'),
+                                prefix_old=name('se_op.se_reduce'), **wide())
+        shared += compress_conv(new_e, m.se_op.se_expand, segs, dim=0, prefix_new=name('se_op.se_expand'),
+                                prefix_old=name('se_op.se_expand'), **wide())
+    shared += compress_conv(new_project[0] if alive else None, old_project[0], segs, dim=1, prefix_new=name('project_conv.0'),
+                            prefix_old=name('project_conv.0'), **wide())
+    name_bn = name('project_conv.1')
+    if alive:
+        out_bn_infos = adjust_bn(new_project[1], old_project[1], None, prefix_new=name_bn, prefix_old=name_bn)
+    else:
+        out_bn_infos = compress_bn(None, old_project[1], None, prefix_new=name_bn, prefix_old=name_bn)
+
+    keep_infos, drop_infos = [], []
+    new_padded = _scatter_by_bool(list(new_depth), keeps)
+    new_idx_padded = _scatter_by_bool(list(range(len(new_depth))), keeps)
+    for new_op, new_i, old_op, old_i, mask in zip(new_padded, new_idx_padded, m.depth_ops, range(len(m.depth_ops)), masks):
+        old_cbr = list(old_op.children())[1]
+        new_cbr = None if new_op is None else list(new_op.children())[1]
+        (drop_infos if new_op is None else keep_infos).append(
+            compress_conv_bn_relu(new_cbr, old_cbr, mask, name('depth_ops.{}.1'.format(new_i)), name('depth_ops.{}.1'.format(old_i))))
+
+    if ema is not None:
+        ema.compress_start()
+    if prune_info is not None:
+        prune_info.compress_start()
+    if alive:
+        update(out_bn_infos)       # the tensors that keep their names first, as the plain block's pw_bn
+        update(shared)
+        for infos in keep_infos:   # ascending: a renumbered branch only ever takes the name of a dropped or already moved one
+            update(infos)
+    else:
+        clean(out_bn_infos)
+        clean(shared)
+    for infos in drop_infos:       # dropped branches last
+        clean(infos)
+
+    del m.expand_conv, m.depth_ops, m.project_conv, m.se_op
+    m.expand_conv, m.depth_ops, m.project_conv, m.se_op = new_expand, new_depth, new_project, new_se
+    _swap_done(m)

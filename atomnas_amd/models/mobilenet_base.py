@@ -201,6 +201,8 @@ class InvertedResidualChannelsFused(nn.Module):
     def _build(self, hidden_dims, kernel_sizes, expand, se_ratio):
         bn_kw = self.batch_norm_kwargs if self.batch_norm_kwargs is not None else {}
         total = sum(hidden_dims)
+        if expand and total == 0:   # every atom pruned (or a searched row with hiddens == []): the identity, no tensor left
+            return Identity(), nn.ModuleList(), Identity(), Identity()
         expand_conv = (ConvBNReLU(self.input_dim, total, kernel_size=1, batch_norm_kwargs=bn_kw, active_fn=self.active_fn)
                        if self.expand else Identity())
         depth_ops = nn.ModuleList()
@@ -236,6 +238,10 @@ class InvertedResidualChannelsFused(nn.Module):
         return list(self.get_named_depthwise_bn().values())
 
     def forward(self, x):
+        if len(self.depth_ops) == 0:
+            if not self.use_res_connect:
+                logging.warning('The whole block is pruned without skip connection')
+            return x
         mgr = runtime.manager_of(self)
         mgr.enter()
         try:
@@ -247,6 +253,16 @@ class InvertedResidualChannelsFused(nn.Module):
         return '{}({}, {}, channels={}, kernel_sizes={}, expand={}, stride={}, se_ratio={})'.format(
             self._get_name(), self.input_dim, self.output_dim, self.channels, self.kernel_sizes, self.expand, self.stride,
             self.se_ratio)
+
+    # -- dynamic shrinkage
+    def compress_by_mask(self, masks, **kwargs):
+        """Rebuilds the block keeping only the atoms whose mask is True (per-branch bool tensors, in branch order)."""
+        from . import compress_utils as cu
+        cu.compress_inverted_residual_channels_fused(self, masks, **kwargs)
+
+    def compress_by_threshold(self, threshold, **kwargs):
+        masks = [bn.weight.detach().abs() > threshold for bn in self.get_depthwise_bn()]
+        self.compress_by_mask(masks, **kwargs)
 
 
 _ACTIVATIONS = {
@@ -308,8 +324,13 @@ def output_network(model):
     supernet is exported as (checkpoint `.yml`)."""
     kwargs = {key: getattr(model, key) for key in
               ['input_channel', 'last_channel', 'width_mult', 'round_nearest', 'active_fn', 'num_classes']}
-    kwargs['inverted_residual_setting'] = [[b.output_dim, 1, b.stride, b.kernel_sizes, b.channels, b.expand]
-                                           for b in model.get_named_block_list().values()]
+    blocks = list(model.get_named_block_list().values())
+    kwargs['inverted_residual_setting'] = [[b.output_dim, 1, b.stride, b.kernel_sizes, b.channels, b.expand] for b in blocks]
+    if blocks and all(isinstance(b, InvertedResidualChannelsFused) for b in blocks):
+        # a fused search exports what `searched_network` needs to rebuild the same blocks; a plain model's dict stays as it was
+        kwargs['block'] = 'InvertedResidualChannelsFused'
+        if getattr(model, 'se_ratio', None) is not None:
+            kwargs['se_ratio'] = model.se_ratio
     return kwargs
 
 

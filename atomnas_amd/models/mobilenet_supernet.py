@@ -10,14 +10,21 @@ from torch import nn
 
 from .. import functional as AF
 from .. import runtime
-from .mobilenet_base import ConvBNReLU, _get_named_block_list, _make_divisible, get_active_fn, get_block
+from .mobilenet_base import (ConvBNReLU, InvertedResidualChannelsFused, _get_named_block_list, _make_divisible, get_active_fn,
+                             get_block)
 
 __all__ = ['MobileNetV2']
 
 
-def get_block_wrapper(block_str):
-    """Block class that takes an expand ratio (number or per-branch list) instead of explicit hidden widths (:14-55)."""
+def get_block_wrapper(block_str, se_ratio=None):
+    """Block class that takes an expand ratio (number or per-branch list) instead of explicit hidden widths (:14-55).  se_ratio: the
+    Squeeze-and-Excitation ratio of a fused block (width int(round(inp * se_ratio)), as in the searched network)."""
     base = get_block(block_str)
+    extra = {}
+    if se_ratio is not None:
+        if not issubclass(base, InvertedResidualChannelsFused):
+            raise NotImplementedError('SE module not supported for block: {}'.format(base))
+        extra['se_ratio'] = se_ratio
 
     class InvertedResidual(base):
 
@@ -31,7 +38,7 @@ def get_block_wrapper(block_str):
                 raise ValueError('Unknown expand_ratio type: {}'.format(expand_ratio))
             hidden = [int(round(inp * r)) for r in ratios]
             super().__init__(inp, oup, stride, hidden, kernel_sizes, expand, active_fn=active_fn,
-                             batch_norm_kwargs=batch_norm_kwargs)
+                             batch_norm_kwargs=batch_norm_kwargs, **extra)
             self.expand_ratio = ratios if isinstance(expand_ratio, list) else ratios
 
     return InvertedResidual
@@ -89,13 +96,13 @@ class MobileNetV2(_HipModel):
 
     def __init__(self, num_classes=1000, input_size=224, input_channel=32, last_channel=1280, width_mult=1.0,
                  inverted_residual_setting=None, dropout_ratio=0.2, batch_norm_momentum=0.1, batch_norm_epsilon=1e-5,
-                 active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8):
+                 active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8, se_ratio=None):
         super().__init__()
         bn_kw = {'momentum': batch_norm_momentum, 'eps': batch_norm_epsilon}
         self.input_size, self.input_channel, self.last_channel = input_size, input_channel, last_channel
         self.num_classes, self.width_mult, self.round_nearest = num_classes, width_mult, round_nearest
         self.inverted_residual_setting = inverted_residual_setting
-        self.active_fn, self.block, self.batch_norm_kwargs = active_fn, block, bn_kw
+        self.active_fn, self.block, self.batch_norm_kwargs, self.se_ratio = active_fn, block, bn_kw, se_ratio
 
         if not inverted_residual_setting or len(inverted_residual_setting[0]) != 5:
             raise ValueError('inverted_residual_setting should be non-empty or a 5-element list, got {}'.format(
@@ -103,7 +110,7 @@ class MobileNetV2(_HipModel):
         if input_size % 32 != 0:
             raise ValueError('Input size must divide 32')
         act = get_active_fn(active_fn)
-        block_cls = get_block_wrapper(block)
+        block_cls = get_block_wrapper(block, se_ratio)
 
         width = _make_divisible(input_channel * width_mult, round_nearest)
         final = _make_divisible(last_channel * max(1.0, width_mult), round_nearest)

@@ -22,7 +22,7 @@ class MobileNetSearched(_HipModel):
         self.input_size, self.input_channel, self.last_channel = input_size, input_channel, last_channel
         self.num_classes, self.width_mult, self.round_nearest = num_classes, width_mult, round_nearest
         self.inverted_residual_setting = inverted_residual_setting
-        self.active_fn, self.block, self.batch_norm_kwargs = active_fn, block, bn_kw
+        self.active_fn, self.block, self.batch_norm_kwargs, self.se_ratio = active_fn, block, bn_kw, se_ratio
 
         if not inverted_residual_setting or len(inverted_residual_setting[0]) != 6:
             raise ValueError('inverted_residual_setting should be non-empty or a 6-element list, got {}'.format(

@@ -197,9 +197,10 @@ class ArenaLayout:
         pl.nb = len(branches)
         pl.se = fused and isinstance(m.se_op, mb.SqueezeAndExcitation)
         if pl.nb == 0:
-            # an all-pruned block keeps only its (unused) pw_bn; give it ordinary slots
+            # an all-pruned block keeps only its (unused) pw_bn; give it ordinary slots.  The fused block keeps nothing
             pl.HT = 0
-            self.bind_bn(m.pw_bn, self.bn_slots(oup), 0, oup)
+            if not fused:
+                self.bind_bn(m.pw_bn, self.bn_slots(oup), 0, oup)
             return self._done(m, pl)
         # expanding blocks keep their hidden tensors slab-major (segments = whole 16-channel slabs); the first block of the network (no
         # expansion: hidden = input, narrow) stays plain with 8-channel padding

@@ -61,6 +61,25 @@ class PruneInfo(object):
         return self._info.pop(name)
 
 
+def _fused_atom_costs(m, named_bns):
+    """MACs an expanding fused block loses with one atom of branch i, from the stamps of utils.model_profiling: the atom's row of the
+    shared expand conv, its depthwise filter, its column of the shared projection and, with SE, its share of the gate (its pixels of the
+    squeeze, its column of se_reduce and its row of se_expand):  inp*H*W + k_i^2*Ho*Wo + oup*Ho*Wo (+ Ho*Wo + 2*se_hid).  Every shared
+    layer is linear in the hidden width, so the shares are exact integers and sum_i hidden_i * cost_i == m.n_macs."""
+    hiddens = [bn.weight.numel() for bn in named_bns.values()]
+    total = sum(hiddens)
+    if total == 0:   # every atom already pruned: the identity, nothing to penalise
+        return []
+    shared = m.expand_conv.n_macs + m.project_conv.n_macs + getattr(m.se_op, 'n_macs', 0)
+    assert shared % total == 0, (shared, total)
+    costs = []
+    for op, hidden in zip(m.depth_ops, hiddens):
+        assert op.n_macs % hidden == 0, (op.n_macs, hidden)
+        costs.append(shared // total + op.n_macs // hidden)
+    assert sum(h * c for h, c in zip(hiddens, costs)) == m.n_macs
+    return costs
+
+
 def get_bn_to_prune(model, flags, verbose=True):
     """PruneInfo over the depthwise-BN gammas of every (expanding) block; penalty = per-channel MACs normalised so that the
     atom-weighted mean is 1 (utils/prune.py:89-158).  Needs the `n_macs` stamps of utils.model_profiling."""
@@ -69,13 +88,16 @@ def get_bn_to_prune(model, flags, verbose=True):
     if bn_prune_filter in ('expansion_only', 'expansion_only_skip_expand1', 'equal_penalty_skip_expand1'):
         pairs = []
         for name, m in model.get_named_block_list().items():
-            if not isinstance(m, mb.InvertedResidualChannels):
+            if not isinstance(m, (mb.InvertedResidualChannels, mb.InvertedResidualChannelsFused)):
                 continue
             if bn_prune_filter.endswith('skip_expand1') and not m.expand:
                 continue
-            for op, (bn_name, bn) in zip(m.ops, m.get_named_depthwise_bn(prefix=name).items()):
-                hidden = bn.weight.numel()
-                pairs.append((hidden, op.n_macs / hidden))
+            if isinstance(m, mb.InvertedResidualChannelsFused):
+                costs = _fused_atom_costs(m, m.get_named_depthwise_bn(prefix=name))
+            else:
+                costs = [op.n_macs / bn.weight.numel() for op, bn in zip(m.ops, m.get_depthwise_bn())]
+            for cost, (bn_name, bn) in zip(costs, m.get_named_depthwise_bn(prefix=name).items()):
+                pairs.append((bn.weight.numel(), cost))
                 weights.append('{}.weight'.format(bn_name))
         pcf = [v for _, v in pairs]
         if bn_prune_filter.startswith('equal_penalty'):

@@ -66,8 +66,9 @@ def shrink_model(model_wrapper, ema, optimizer, prune_info, threshold=1e-3, ema_
     blocks = list(model.get_named_block_list().items())
     gammas, per_block = [], []
     for block_name, block in blocks:
-        assert isinstance(block, mb.InvertedResidualChannels)
-        bns = block.get_depthwise_bn()
+        assert isinstance(block, (mb.InvertedResidualChannels, mb.InvertedResidualChannelsFused))
+        # a fused block that does not expand has no atoms to search: it is left alone
+        bns = block.get_depthwise_bn() if block.expand or isinstance(block, mb.InvertedResidualChannels) else []
         per_block.append(len(bns))
         gammas.extend(bn.weight for bn in bns)
     if ema is not None:
@@ -86,6 +87,8 @@ def shrink_model(model_wrapper, ema, optimizer, prune_info, threshold=1e-3, ema_
         for (block_name, block), n in zip(blocks, per_block):
             masks = all_masks[pos:pos + n]
             pos += n
+            if n == 0 and isinstance(block, mb.InvertedResidualChannelsFused):
+                continue   # not searched, or already the identity: no tensor to repack
             block.compress_by_mask(masks, ema=ema, optimizer=optimizer, prune_info=prune_info, prefix=block_name, verbose=False)
     finally:
         ops.gather_defer(False)   # flush
