@@ -357,6 +357,107 @@ __global__ __launch_bounds__(256) void k_act_bwd_stats(const T* __restrict__ dy,
   }
 }
 
+// ---- stochastic depth (drop-connect, torchvision StochasticDepth mode "row") of a residual block: the keep decision of image n
+__device__ __forceinline__ bool drop_connect_keep(unsigned long long seed, unsigned long long step, int block_index, int n, float drop_p) {
+  // the constant's low bits are set, the tail dropout's key has none below bit 20: the two never draw from the same key
+  const unsigned long long key = seed ^ (step * 0x100000001B3ull) ^ 0xD1B54A32D192ED03ull ^ ((unsigned long long)block_index << 40) ^
+                                 ((unsigned long long)n << 8);
+  return ((float)(hash32(key) >> 8) * (1.0f / 16777216.0f)) >= drop_p;
+}
+
+// y = res + keep[n] / (1 - p) * (x*scale + shift), 8 channels per thread: the block's pw_bn apply + residual with the branch dropped
+// per image.  A dropped image copies res (a select: its x rows are not read); the first thread of an image stores keep_out[n].
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_apply_drop(const T* __restrict__ x, int ldx, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, const T* __restrict__ res, int ldres,
+                                                       T* __restrict__ y, int ldy, unsigned char* __restrict__ keep_out, float drop_p,
+                                                       unsigned long long seed, const long long* __restrict__ step_ptr, int block_index,
+                                                       int N, int HW, int C) {
+  const int cg = (C + 7) / 8;
+  const long per_image = (long)HW * cg;
+  const long total = (long)N * per_image;
+  const float keep_scale = 1.0f / (1.0f - drop_p);
+  const unsigned long long step = step_ptr ? (unsigned long long)step_ptr[0] : 0ull;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long m = i / cg;
+    const int c0 = (int)(i % cg) * 8;
+    const int n = (int)(m / HW);
+    const bool k = drop_connect_keep(seed, step, block_index, n, drop_p);
+    if (i == (long)n * per_image) keep_out[n] = k ? 1 : 0;
+    float v[8];
+    VecIO<T, 8>::load(res + m * ldres + c0, v);
+    if (k) {
+      float a[8], s[8], h[8];
+      VecIO<T, 8>::load(x + m * ldx + c0, a);
+      VecIO<float, 8>::load(scale + c0, s);
+      VecIO<float, 8>::load(shift + c0, h);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += keep_scale * (a[e] * s[e] + h[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (c0 + e >= C) v[e] = 0.f;
+    VecIO<T, 8>::store(y + m * ldy + c0, v);
+  }
+}
+
+// backward of the drop: gs = round_T(keep[n] / (1 - p) * g), exact zeros for a dropped image (its g / z rows are not read);
+// stats2 rows = [sum gs, sum gs*z] over the values as stored.  Geometry and row layout of k_act_bwd_stats.
+template <typename T>
+__global__ __launch_bounds__(256) void k_drop_connect_bwd(const T* __restrict__ g, int ldg, const T* __restrict__ z, int ldz,
+                                                          const unsigned char* __restrict__ keep, float drop_p, T* __restrict__ gs,
+                                                          int ldgs, float* __restrict__ stats2, int stat_rows, long M, int HW, int C,
+                                                          int lcg) {
+  __shared__ float s_red[256 * 16];   // [pixel lane][channel of the block column][2]
+  const int tid = threadIdx.x;
+  const int CGL = 1 << lcg, PL = 256 >> lcg;
+  const int cgl = tid & (CGL - 1), pl = tid >> lcg;
+  const int c0 = (blockIdx.y * CGL + cgl) * 8;
+  const float keep_scale = 1.0f / (1.0f - drop_p);
+  float s0[8], s1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
+  if (c0 < C) {
+    for (long p = (long)blockIdx.x * PL + pl; p < M; p += (long)gridDim.x * PL) {
+      float d[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d[e] = 0.f;
+      if (keep[p / HW]) {
+        float v[8];
+        VecIO<T, 8>::load(g + p * ldg + c0, d);
+        VecIO<T, 8>::load(z + p * ldz + c0, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float gg = (c0 + e < C) ? d[e] * keep_scale : 0.f;
+          gg = to_f32(from_f32<T>(gg));
+          d[e] = gg;
+          s0[e] += gg;
+          s1[e] += gg * v[e];
+        }
+      }
+      VecIO<T, 8>::store(gs + p * ldgs + c0, d);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    s_red[(pl * CGL * 8 + cgl * 8 + e) * 2] = s0[e];
+    s_red[(pl * CGL * 8 + cgl * 8 + e) * 2 + 1] = s1[e];
+  }
+  __syncthreads();
+  if (tid < CGL * 8) {
+    const int c = blockIdx.y * CGL * 8 + tid;
+    if (c < C) {
+      float a = 0.f, b = 0.f;
+      for (int q = 0; q < PL; ++q) { a += s_red[(q * CGL * 8 + tid) * 2]; b += s_red[(q * CGL * 8 + tid) * 2 + 1]; }
+      float* srow = stats2 + (long)blockIdx.x * 2 * C;   // one row per workgroup column (gridDim.x <= stat_rows)
+      srow[c] = a;
+      srow[C + c] = b;
+      stat_zero_tail(stats2, 2L * C, blockIdx.x + gridDim.x, gridDim.x, stat_rows, c);
+      stat_zero_tail(stats2, 2L * C, blockIdx.x + gridDim.x, gridDim.x, stat_rows, C + c);
+    }
+  }
+}
+
 }  // namespace atomnas
 
 using namespace atomnas;
@@ -494,4 +595,49 @@ extern "C" int atomnas_act_bwd_stats(const void* dy, int lddy, const void* z, in
     hipLaunchKernelGGL(k_act_bwd_stats<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dy, lddy, (const bf16_t*)z, ldz, scale, shift,
                        relu, (bf16_t*)g, ldg, stats2, stat_rows, M, C, lcg);
   return check_launch("act_bwd_stats");
+}
+
+extern "C" int atomnas_bn_apply_drop(const void* x, int ldx, const float* scale, const float* shift, const void* res, int ldres, void* y,
+                                     int ldy, unsigned char* keep_out, float drop_p, unsigned long long seed, const long long* step_ptr,
+                                     int block_index, int N, int HW, int C, int dtype, void* stream) {
+  ATOMNAS_REQUIRE(x && y && scale && shift && res && keep_out && N > 0 && HW > 0 && C > 0, "bn_apply_drop: bad arguments (the residual is required)");
+  ATOMNAS_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && ldres % 8 == 0 && ldx >= C && ldy >= C && ldres >= C, "bn_apply_drop: bad pitch");
+  ATOMNAS_REQUIRE(drop_p > 0.f && drop_p < 1.f, "bn_apply_drop: the drop rate must lie in (0, 1)");
+  ATOMNAS_REQUIRE(block_index >= 0 && block_index < (1 << 23), "bn_apply_drop: bad block index");
+  const long total = (long)N * HW * ((C + 7) / 8);
+  long blocks = (total + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(k_bn_apply_drop<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, ldx, scale, shift,
+                       (const float*)res, ldres, (float*)y, ldy, keep_out, drop_p, seed, step_ptr, block_index, N, HW, C);
+  else
+    hipLaunchKernelGGL(k_bn_apply_drop<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, ldx, scale, shift,
+                       (const bf16_t*)res, ldres, (bf16_t*)y, ldy, keep_out, drop_p, seed, step_ptr, block_index, N, HW, C);
+  return check_launch("bn_apply_drop");
+}
+
+extern "C" int atomnas_drop_connect_bwd(const void* g, int ldg, const void* z, int ldz, const unsigned char* keep, float drop_p, void* gs,
+                                        int ldgs, float* stats2, int stat_rows, int N, int HW, int C, int dtype, void* stream) {
+  ATOMNAS_REQUIRE(g && z && keep && gs && stats2 && N > 0 && HW > 0 && C > 0, "drop_connect_bwd: bad arguments");
+  ATOMNAS_REQUIRE(ldg % 8 == 0 && ldz % 8 == 0 && ldgs % 8 == 0 && ldg >= C && ldz >= C && ldgs >= C, "drop_connect_bwd: bad pitch");
+  ATOMNAS_REQUIRE(drop_p > 0.f && drop_p < 1.f, "drop_connect_bwd: the drop rate must lie in (0, 1)");
+  ATOMNAS_REQUIRE(stat_rows > 0, "drop_connect_bwd: statistics need stat_rows > 0");
+  const long M = (long)N * HW;
+  const int ncg = (C + 7) / 8;
+  int lcg = 0;
+  while ((1 << lcg) < ncg && lcg < 5) ++lcg;   // channel groups per block column, as atomnas_act_bwd_stats
+  const int cgl = 1 << lcg, pl = 256 >> lcg;
+  long gx = (M + pl - 1) / pl;
+  if (gx > 2048) gx = 2048;
+  if (gx > stat_rows) gx = stat_rows;
+  dim3 grid((unsigned)gx, (ncg + cgl - 1) / cgl);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(k_drop_connect_bwd<float>, grid, dim3(256), 0, st, (const float*)g, ldg, (const float*)z, ldz, keep, drop_p,
+                       (float*)gs, ldgs, stats2, stat_rows, M, HW, C, lcg);
+  else
+    hipLaunchKernelGGL(k_drop_connect_bwd<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)g, ldg, (const bf16_t*)z, ldz, keep, drop_p,
+                       (bf16_t*)gs, ldgs, stats2, stat_rows, M, HW, C, lcg);
+  return check_launch("drop_connect_bwd");
 }

@@ -144,6 +144,7 @@ PROJECT_BWD_FUSED_MAX_OUP = 48
 # inp <= 64).  48 = stages 1-3 with the streaming kernel k_expand_bwd_s (same-box A/Bs: 31.15 -> 30.20 ms for inp <= 24, -> 30.11 with
 # the per-segment launches of 40 -> 720; the 31.41 of profiles/r04_expand_bwd_noe_ab.txt for 48 predates that kernel)
 EXPAND_BWD_NOE_MAX_INP = 48
+DROP_CONNECT_SEED = 1995   # stochastic depth of a block used on its own (no enclosing model with a `dropout_seed`): the models' default seed
 TAIL_TAP = None   # set to a list by tests to receive the dropout keep mask of every tail forward
 # set to a list by tests to receive, for every activation the forward applies, (kind, plan, raw tensor, scale, shift): the pre-activation
 # is raw * scale + shift per channel -- what a test needs to compare ReLU masks with the oracle's (tests/test_block_gpu.py)
@@ -277,9 +278,33 @@ def block_forward(pl, x2d, N, H, W, need_grad):
     ops.gemm_nt(wp=pl.Wp_pack, c=Pr, M=M2, N=pl.oup, K=HT, **_pro("a", *A), **_fwd_stats(stP))
     bP = bn_forward_coeffs(pl.bnp, stP, M2, dev)
     out = torch.empty(M2, pl.oup, dtype=T, device=dev)
-    ops.bn_apply(Pr, bP.scale, bP.shift, False, x2d if pl.res else None, out, M2, pl.oup)
+    drop_p, keep = _drop_rate(pl), None
+    if drop_p > 0:
+        # stochastic depth: the same launch slot, with the branch dropped per image behind the (undropped) block-output BatchNorm
+        keep = pl.drop_keep = torch.empty(N, dtype=torch.uint8, device=dev)
+        ops.bn_apply_drop(Pr, bP.scale, bP.shift, x2d, out, keep, drop_p, getattr(pl.mgr.model, "dropout_seed", DROP_CONNECT_SEED),
+                          pl.mgr.step_counter, pl.module.drop_connect_index, N, Ho * Wo, pl.oup)
+    else:
+        ops.bn_apply(Pr, bP.scale, bP.shift, False, x2d if pl.res else None, out, M2, pl.oup)
     _stap(pl, E=E if pl.expand else None, bne=bE, D=D, bnd=bD, P=Pr, bnp=bP, out=out)
-    return out, dict(x=x2d, E=E, D=D, P=Pr, bE=bE, bD=bD, bP=bP, dims=(N, H, W, Ho, Wo), se=se, A=A) if need_grad else None
+    if not need_grad:
+        return out, None
+    return out, dict(x=x2d, E=E, D=D, P=Pr, bE=bE, bD=bD, bP=bP, dims=(N, H, W, Ho, Wo), se=se, A=A, keep=keep, drop_p=drop_p)
+
+
+def _drop_rate(pl):
+    """stochastic-depth rate of this forward: the module's drop_connect_rate for a residual block in training mode, else 0"""
+    m = pl.module
+    return float(m.drop_connect_rate) if pl.res and m.training else 0.0
+
+
+def drop_connect_keep(block):
+    """uint8 [N] keep decisions (1 = branch kept) of the last training forward of `block` (an InvertedResidualChannels[Fused] module)
+    that ran with stochastic depth, None if it never did.  Every forward allocates its own tensor (as the tail dropout does), so
+    "last" is the last forward that ran in Python: a captured step's tensor is rewritten by every replay of that graph, and of the two
+    graphs of a captured accumulated step this is the one captured last."""
+    pl = getattr(block, "_plan", None)
+    return getattr(pl, "drop_keep", None) if pl is not None else None
 
 
 def project_bwd_form(pl, T, M2, G, D, g, stat_rows):
@@ -320,12 +345,19 @@ def block_backward(pl, sv, G):
     x2d, E, D, bE = sv["x"], sv["E"], sv["D"], sv["bE"]
     # pw_bn backward: statistics pass over (G, P), then coefficients
     st2P = _stats(pl.oup, dev, pl.bnp["mgr"])
-    ops.act_bwd_stats(G, sv["P"], None, None, False, None, st2P.t, M2, pl.oup, stat_rows=st2P.rows)
+    if sv["keep"] is not None:
+        # stochastic depth: the branch receives Gs = keep[n] / (1 - p) * G (the same launch slot writes it with its statistics); the
+        # residual path below keeps G
+        Gb = torch.empty(M2, pl.oup, dtype=T, device=dev)
+        ops.drop_connect_bwd(G, sv["P"], sv["keep"], sv["drop_p"], Gb, st2P.t, N, Ho * Wo, pl.oup, stat_rows=st2P.rows)
+    else:
+        Gb = G
+        ops.act_bwd_stats(G, sv["P"], None, None, False, None, st2P.t, M2, pl.oup, stat_rows=st2P.rows)
     p = bn_backward_coeffs(pl.bnp, sv["bP"], st2P, M2, dev)
     # projection backward by form: g = gradient wrt the dw_bn output, with the dw_bn backward statistics
     g = _hidden(pl, M2, HT, T, dev)
     st2D = _stats(HT, dev, pl.bnd["mgr"])
-    dP = _project_backward(pl, project_bwd_form(pl, T, M2, G, D, g, st2D.rows), sv, G, p, g, st2D)
+    dP = _project_backward(pl, project_bwd_form(pl, T, M2, Gb, D, g, st2D.rows), sv, Gb, p, g, st2D)
     d1, d2, d3 = d = bn_backward_coeffs(pl.bnd, sv["bD"], st2D, M2, dev)
     # depthwise backward per branch
     h = _hidden(pl, M, HT if pl.expand else pl.inp, T, dev)

@@ -110,6 +110,11 @@ class InvertedResidualChannels(nn.Module):
     out = pw_bn(sum_i project_i(dw_i(expand_i(x)))) (+ x when stride == 1 and inp == oup); an empty `ops` is the identity.
     """
 
+    # stochastic depth (functional.block_forward): the rate this block's branch is dropped with per image in training mode and the
+    # block's position in the network, which keys its mask; assigned by the model (set_drop_connect_rate), not constructor arguments
+    drop_connect_rate = 0.0
+    drop_connect_index = 0
+
     def __init__(self, inp, oup, stride, channels, kernel_sizes, expand, active_fn=None, batch_norm_kwargs=None):
         super().__init__()
         assert stride in [1, 2]
@@ -185,6 +190,11 @@ class InvertedResidualChannelsFused(nn.Module):
     Numerically it IS the branch block with concatenated weights, which is how the HIP executor always runs a block, so the
     forward dispatches to the same executor (functional.block_forward) with the SE stage between depthwise and projection.
     """
+
+    # stochastic depth (functional.block_forward): the rate this block's branch is dropped with per image in training mode and the
+    # block's position in the network, which keys its mask; assigned by the model (set_drop_connect_rate), not constructor arguments
+    drop_connect_rate = 0.0
+    drop_connect_index = 0
 
     def __init__(self, inp, oup, stride, channels, kernel_sizes, expand, active_fn=None, batch_norm_kwargs=None,
                  se_ratio=None):

@@ -63,6 +63,20 @@ class _HipModel(nn.Module):
     def get_named_block_list(self):
         return _get_named_block_list(self)
 
+    def set_drop_connect_rate(self, rate):
+        """Stochastic depth (EfficientNet's drop_connect_rate): in training mode block b of the B blocks of get_named_block_list() drops
+        its branch per image with probability rate * b / B, so the first block never drops.  Only blocks with a residual connection
+        are affected; 0 turns it off."""
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError('drop_connect_rate must lie in [0, 1), got {}'.format(rate))
+        blocks = list(self.get_named_block_list().values())
+        for b, blk in enumerate(blocks):
+            blk.drop_connect_rate = rate * b / len(blocks)
+            blk.drop_connect_index = b
+        self.drop_connect_rate = rate
+        return self
+
     def forward(self, x, loss_args=None):
         """loss_args (engine.TrainStep only): (target, label_smoothing, loss_vec, topk, loss_out) -- the tail and the
         label-smoothed cross entropy then run as one autograd node and the scalar mean loss is returned instead of the logits."""
@@ -96,7 +110,7 @@ class MobileNetV2(_HipModel):
 
     def __init__(self, num_classes=1000, input_size=224, input_channel=32, last_channel=1280, width_mult=1.0,
                  inverted_residual_setting=None, dropout_ratio=0.2, batch_norm_momentum=0.1, batch_norm_epsilon=1e-5,
-                 active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8, se_ratio=None):
+                 active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8, se_ratio=None, drop_connect_rate=0.0):
         super().__init__()
         bn_kw = {'momentum': batch_norm_momentum, 'eps': batch_norm_epsilon}
         self.input_size, self.input_channel, self.last_channel = input_size, input_channel, last_channel
@@ -124,6 +138,7 @@ class MobileNetV2(_HipModel):
         layers.append(nn.AvgPool2d(input_size // 32))
         self.features = nn.Sequential(*layers)
         self.classifier = nn.Sequential(nn.Dropout(dropout_ratio), nn.Linear(final, num_classes))
+        self.set_drop_connect_rate(drop_connect_rate)
 
 
 Model = MobileNetV2

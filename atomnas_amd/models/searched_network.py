@@ -14,7 +14,8 @@ class MobileNetSearched(_HipModel):
 
     def __init__(self, num_classes=1000, input_size=224, input_channel=32, last_channel=1280, width_mult=1.0,
                  inverted_residual_setting=None, dropout_ratio=0.2, se_ratio=None, batch_norm_momentum=0.1,
-                 batch_norm_epsilon=1e-5, active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8):
+                 batch_norm_epsilon=1e-5, active_fn='nn.ReLU6', block='InvertedResidualChannels', round_nearest=8,
+                 drop_connect_rate=0.0):
         super().__init__()
         bn_kw = {'momentum': batch_norm_momentum, 'eps': batch_norm_epsilon}
         if width_mult != 1.0:
@@ -51,6 +52,7 @@ class MobileNetSearched(_HipModel):
         layers.append(nn.AvgPool2d(input_size // 32))
         self.features = nn.Sequential(*layers)
         self.classifier = nn.Sequential(nn.Dropout(dropout_ratio), nn.Linear(last_channel, num_classes))
+        self.set_drop_connect_rate(drop_connect_rate)
 
 
 Model = MobileNetSearched

@@ -462,6 +462,26 @@ def act_bwd_stats(dy, z, scale, shift, relu, g, stats2, M, C, stat_rows=None):
          _ld(g) if g is not None else 0, _p(stats2), _rows(stats2, stat_rows), M, C, dt_code(dy.dtype), _stream())
 
 
+def bn_apply_drop(x, scale, shift, res, y, keep_out, drop_p, seed, step_ptr, block_index, N, HW, C):
+    """y = res + keep[n] / (1 - drop_p) * (x * scale + shift) per image n (stochastic depth): the block's bn_apply launch with the
+    branch dropped per image; keep_out: uint8 [N], written"""
+    _chk_cuda(x, res, y, keep_out)
+    _rec("bn_apply_drop", N=int(N), HW=int(HW), C=int(C), x=_lay(x), res=_lay(res), y=_lay(y), drop_p=float(drop_p), block=int(block_index),
+         dt=dt_code(x.dtype))
+    call("atomnas_bn_apply_drop", _p(x), _ld(x), _p(scale), _p(shift), _p(res), _ld(res) if res is not None else 0, _p(y), _ld(y), _p(keep_out), float(drop_p),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_ptr), int(block_index), N, HW, C, dt_code(x.dtype), _stream())
+
+
+def drop_connect_bwd(g, z, keep, drop_p, gs, stats2, N, HW, C, stat_rows=None):
+    """gs = keep[n] / (1 - drop_p) * g per image n, stats2 rows [sum gs, sum gs * z]: the act_bwd_stats launch in front of the
+    block-output BatchNorm backward, with the gradient of the dropped branch"""
+    _chk_cuda(g, z, keep, gs)
+    _rec("drop_connect_bwd", N=int(N), HW=int(HW), C=int(C), g=_lay(g), z=_lay(z), gs=_lay(gs), drop_p=float(drop_p),
+         stat_rows=_rows(stats2, stat_rows), dt=dt_code(g.dtype))
+    call("atomnas_drop_connect_bwd", _p(g), _ld(g), _p(z), _ld(z), _p(keep), float(drop_p), _p(gs), _ld(gs), _p(stats2),
+         _rows(stats2, stat_rows), N, HW, C, dt_code(g.dtype), _stream())
+
+
 def se_pool_parts(N, HW, C):
     """planes [parts][N][C] the per-image sums of se_squeeze / se_bwd_gate's dgate pass are produced in (include/atomnas_hip.h)"""
     return int(_lib.load().atomnas_se_pool_parts(int(N), int(HW), int(C)))

@@ -205,6 +205,26 @@ int atomnas_pool_act_bwd(const void* dpooled, int ldp, const unsigned char* keep
 /* g = dy * [z*scale+shift > 0] (scale == NULL: no mask);  stats2 rows [sum g, sum g*z];  g may be NULL (statistics only) */
 int atomnas_act_bwd_stats(const void* dy, int lddy, const void* z, int ldz, const float* scale, const float* shift, int relu, void* g,
                           int ldg, float* stats2, int stat_rows, long M, int C, int dtype, void* stream);
+/* ---- stochastic depth (drop-connect; torchvision StochasticDepth mode "row") of a residual block, x / res / y: [N*HW][C].
+ * atomnas_bn_apply_drop takes the place of the block's atomnas_bn_apply: y[n] = res[n] + keep[n] * s * (x[n]*scale + shift) with
+ *   s = 1.0f / (1.0f - drop_p) in fp32, rounded once to the storage type; the image n of a row is row / HW.  A dropped image is a
+ *   copy of res (a select: its x rows are not read, so nothing in them reaches y).  keep_out receives the N decisions as bytes:
+ *     key  = seed ^ (step * 0x100000001B3) ^ 0xD1B54A32D192ED03 ^ ((u64)block_index << 40) ^ ((u64)n << 8)
+ *     keep = (float)(hash32(key) >> 8) * 2^-24 >= drop_p           hash32: the upper word of the splitmix64 finaliser of key
+ *   with step = step_ptr[0] (NULL: 0), as the dropout of atomnas_bn_act_pool draws its mask: that one uses
+ *   key = seed ^ (step * 0x100000001B3) ^ ((u64)(n*C + c) << 20), whose bits below 20 equal the seed term's, while the constant
+ *   here flips some of them -- no key of one is a key of the other.  Requires res != NULL and 0 < drop_p < 1; padding channels of
+ *   the last group of 8 are stored as zero.
+ * atomnas_drop_connect_bwd takes the place of the atomnas_act_bwd_stats(G, P) pass in front of the block-output BatchNorm backward:
+ *   gs[n] = keep[n] * s * g[n] rounded to the storage type (exact zeros for a dropped image, whose g / z rows are not read) and the
+ *   stats2 rows [sum gs, sum gs*z] of the values as stored, in the row layout of atomnas_act_bwd_stats (grid capped by stat_rows,
+ *   tail rows zeroed, no atomics).
+ * Added without an ABI version change (backwards compatible). */
+int atomnas_bn_apply_drop(const void* x, int ldx, const float* scale, const float* shift, const void* res, int ldres, void* y, int ldy,
+                          unsigned char* keep_out, float drop_p, unsigned long long seed, const long long* step_ptr, int block_index,
+                          int N, int HW, int C, int dtype, void* stream);
+int atomnas_drop_connect_bwd(const void* g, int ldg, const void* z, int ldz, const unsigned char* keep, float drop_p, void* gs, int ldgs,
+                             float* stats2, int stat_rows, int N, int HW, int C, int dtype, void* stream);
 
 /* ---- Squeeze-and-Excitation of the fused block (AtomNAS+): models/mobilenet_base.py:93-117 inside :256-267.
  *   A = act(D*scale+shift) is the activated depthwise output (never materialised), D the raw depthwise output [M = N*HW][C];
