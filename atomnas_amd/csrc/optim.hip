@@ -273,17 +273,90 @@ struct PackJob {
   int rows, cols, src_ld, dst_ld, c_off, mode;
 };
 
+// A workgroup walks [PACK_TILE x PACK_TILE] tiles of its job (grid = (PACK_GRID_X, job)); a thread moves 4 consecutive elements: one
+// 16-byte load of the source row where the address allows it, one store of 4 storage elements (8 bytes bf16, 16 bytes fp32) into the
+// destination row, element by element at ragged edges and odd offsets.  Modes 1 and 2 turn the tile through LDS, so that both sides of
+// the transpose are walked along their rows (written straight, every lane of a wave store hit another destination row).  Only elements
+// of the job are written: the padding of the pack buffers is zeroed once and never touched.
+constexpr int PACK_TILE = 64;
+constexpr int PACK_GRID_X = 64;
+
+template <typename D>
+__device__ __forceinline__ void pack_store4(D* __restrict__ d, const float (&v)[4], int cnt) {
+  if (cnt == 4 && (reinterpret_cast<uintptr_t>(d) & (4 * sizeof(D) - 1)) == 0) {
+    VecIO<D, 4>::store(d, v);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < cnt) d[k] = from_f32<D>(v[k]);
+  }
+}
+
+__device__ __forceinline__ void pack_load4(const float* __restrict__ s, float (&v)[4], int cnt) {
+  if (cnt == 4 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+    VecIO<float, 4>::load(s, v);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = k < cnt ? s[k] : 0.f;
+  }
+}
+
+// transposed store of one tile out of LDS: destination row c (tile column), 4 consecutive source rows r per thread
+template <typename D>
+__device__ __forceinline__ void pack_store_t(D* __restrict__ dst, long dst_ld, const float (*tile)[PACK_TILE + 1], int r0, int c0, int rows,
+                                             int cols) {
+  const int rq = (threadIdx.x & 15) * 4;
+#pragma unroll
+  for (int pass = 0; pass < PACK_TILE / 16; ++pass) {
+    const int cl = pass * 16 + (threadIdx.x >> 4);
+    const int cnt = min(4, rows - (r0 + rq));
+    if (c0 + cl < cols && cnt > 0) {
+      const float v[4] = {tile[rq][cl], tile[rq + 1][cl], tile[rq + 2][cl], tile[rq + 3][cl]};
+      pack_store4<D>(dst + (long)(c0 + cl) * dst_ld + r0 + rq, v, cnt);
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ arena, void* __restrict__ packbuf, const PackJob* __restrict__ jobs) {
+  __shared__ float tile[PACK_TILE][PACK_TILE + 1];
   const PackJob jb = jobs[blockIdx.y];
-  const long total = (long)jb.rows * jb.cols;
-  const float* src = arena + jb.src_off;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / jb.cols), c = (int)(i % jb.cols);
-    const float v = src[(long)r * jb.src_ld + c];
-    if (jb.mode == 0) reinterpret_cast<T*>(packbuf)[jb.dst_off + (long)r * jb.dst_ld + jb.c_off + c] = from_f32<T>(v);
-    else if (jb.mode == 1) reinterpret_cast<T*>(packbuf)[jb.dst_off + (long)(jb.c_off + c) * jb.dst_ld + r] = from_f32<T>(v);
-    else reinterpret_cast<float*>(packbuf)[jb.dst_off + (long)c * jb.dst_ld + jb.c_off + r] = v;
+  const float* __restrict__ src = arena + jb.src_off;
+  const int tc = (jb.cols + PACK_TILE - 1) / PACK_TILE;
+  const int ntiles = ((jb.rows + PACK_TILE - 1) / PACK_TILE) * tc;
+  const int cq = (threadIdx.x & 15) * 4, rl = threadIdx.x >> 4;   // a pass covers 16 rows x 64 columns
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int r0 = (t / tc) * PACK_TILE, c0 = (t % tc) * PACK_TILE;
+    const int cnt = min(4, jb.cols - (c0 + cq));
+    if (jb.mode == 0) {
+      T* __restrict__ dst = reinterpret_cast<T*>(packbuf) + jb.dst_off + jb.c_off;
+#pragma unroll
+      for (int pass = 0; pass < PACK_TILE / 16; ++pass) {
+        const int r = r0 + pass * 16 + rl;
+        if (r < jb.rows && cnt > 0) {
+          float v[4];
+          pack_load4(src + (long)r * jb.src_ld + c0 + cq, v, cnt);
+          pack_store4<T>(dst + (long)r * jb.dst_ld + c0 + cq, v, cnt);
+        }
+      }
+      continue;
+    }
+    __syncthreads();   // the previous tile has been read out
+#pragma unroll
+    for (int pass = 0; pass < PACK_TILE / 16; ++pass) {
+      const int rt = pass * 16 + rl;
+      if (r0 + rt < jb.rows && cnt > 0) {
+        float v[4];
+        pack_load4(src + (long)(r0 + rt) * jb.src_ld + c0 + cq, v, cnt);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tile[rt][cq + k] = v[k];
+      }
+    }
+    __syncthreads();
+    if (jb.mode == 1)
+      pack_store_t<T>(reinterpret_cast<T*>(packbuf) + jb.dst_off + (long)jb.c_off * jb.dst_ld, jb.dst_ld, tile, r0, c0, jb.rows, jb.cols);
+    else
+      pack_store_t<float>(reinterpret_cast<float*>(packbuf) + jb.dst_off + jb.c_off, jb.dst_ld, tile, r0, c0, jb.rows, jb.cols);
   }
 }
 
@@ -446,7 +519,7 @@ extern "C" int atomnas_add_i64(long* p, long n, long v, void* stream) {
 
 extern "C" int atomnas_pack_weights(const float* arena, void* packbuf, const void* jobs_dev, int njobs, int dtype, void* stream) {
   ATOMNAS_REQUIRE(arena && packbuf && jobs_dev && njobs > 0, "pack_weights: bad arguments");
-  dim3 grid(32, njobs);
+  dim3 grid(PACK_GRID_X, njobs);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_F32) hipLaunchKernelGGL(k_pack<float>, grid, dim3(256), 0, st, arena, packbuf, (const PackJob*)jobs_dev);
   else hipLaunchKernelGGL(k_pack<bf16_t>, grid, dim3(256), 0, st, arena, packbuf, (const PackJob*)jobs_dev);

@@ -2227,6 +2227,9 @@ static int nt_ws_launch(const NtWsPlan& p, const NtArgs& a) {
 struct NtGenericPlan { int ncg; };   // two 64-channel chunks stay live when there is more than one
 static bool nt_generic_plan(const NtArgs& a, NtGenericPlan& p) {
   p.ncg = a.N > 64 ? 2 : 1;
+  // Small M (the classifier and its input gradient: M = the batch) has few 64-row blocks, and (row block, channel group) items are all
+  // the workgroups there are: one 64-channel chunk per item where two leave CUs without one.  K is not split: same bits.
+  if (p.ncg == 2 && (a.M + 63) / 64 * ((a.N + 127) / 128) < num_cus()) p.ncg = 1;
   return true;
 }
 template <typename T>

@@ -690,9 +690,9 @@ static int tn_dma_launch(const TnDmaPlan& p, const TnArgs& a) {
 using TnSlabKernel = decltype(&k_gemm_tn2<PRO_NONE, PRO_NONE, 2, 1, 128>);
 struct TnSlabPlan { TnSlabKernel kern; int utt, vtt, slab_rows, vt, uz; size_t lds; long chunks, rows; int xcd; unsigned grid; };
 constexpr int SLAB_WIDE_MINNV = 256;
-static bool tn_slab_plan(const TnArgs& a, TnSlabPlan& p) {
-  p.utt = tn_utt(a.NU, false);
-  const bool wide = p.utt >= 4 && p.utt <= 12 && a.NV >= SLAB_WIDE_MINNV;
+static bool tn_slab_plan_as(const TnArgs& a, TnSlabPlan& p, int utt, bool allow_wide) {
+  p.utt = utt;
+  const bool wide = allow_wide && p.utt >= 4 && p.utt <= 12 && a.NV >= SLAB_WIDE_MINNV;
   p.vtt = wide ? 2 : 1, p.slab_rows = wide ? 64 : 128;
   if (for_pair(a.umode, a.vmode, [&](auto um, auto vm) {
         return for_value<2, 4, 6, 12, 10, 20>(p.utt, [&](auto utt) {
@@ -715,6 +715,20 @@ static bool tn_slab_plan(const TnArgs& a, TnSlabPlan& p) {
   if (p.xcd) want = want / 8 * 8;    // equal work per XCD
   tn_split(a.M, want, 0, 1, p.chunks, p.rows);
   p.grid = (unsigned)((p.xcd ? (p.chunks + 7) / 8 * 8 : p.chunks) * tiles);
+  return true;
+}
+// Small M (the classifier's weight gradient: M = the batch, NU 1000, NV 1280) has too few rows for a second chunk, so the output tiles
+// are all the workgroups there are: 80 at twenty accumulator tiles.  Such a plan takes narrower U tiles on 128-row slabs (always one
+// chunk below 512 rows) until there is a workgroup per CU.  The rows are not split and a tile's k-steps keep their order, so every
+// output keeps its bits and no partial buffer appears.
+constexpr long SLAB_SMALL_M = 4 * 128;
+static bool tn_slab_plan(const TnArgs& a, TnSlabPlan& p) {
+  if (!tn_slab_plan_as(a, p, tn_utt(a.NU, false), true)) return false;
+  if (a.M >= SLAB_SMALL_M || p.chunks != 1) return true;
+  for (int utt : {12, 10, 6, 4, 2}) {
+    if ((long)p.vt * p.uz >= num_cus()) break;
+    if (utt < p.utt) tn_slab_plan_as(a, p, utt, false);   // the pair is supported: the first plan was made
+  }
   return true;
 }
 static int tn_slab_launch(const TnSlabPlan& p, const TnArgs& a) {

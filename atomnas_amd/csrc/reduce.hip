@@ -8,33 +8,59 @@
 
 namespace atomnas {
 
-// block = 32 elements x 8 part-groups; part-group pg sums parts pg, pg+8, ... (4 independent accumulators, combined in a
-// fixed tree), then the 8 group sums are added in order 0..7.
-__global__ __launch_bounds__(256) void k_reduce_parts(const float* __restrict__ part, long part_stride, int parts, long n,
-                                                      float* __restrict__ out, int inner, long s_outer, long s_inner) {
-  __shared__ float s_acc[8][32];
-  const int el = threadIdx.x & 31, pg = threadIdx.x >> 5;
-  const long e = (long)blockIdx.x * 32 + el;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < n) {
+// block = RED_EPB elements x 8 part-groups; part-group pg sums parts pg, pg+8, ... (4 independent accumulators, combined in a
+// fixed tree), then the 8 group sums are added in order 0..7.  A lane owns 4 consecutive elements and reads them with one 16-byte load
+// per partial row where the row starts allow it (16-byte aligned base, part_stride a multiple of 4, all 4 elements inside n), element by
+// element otherwise: a wave then reads 512 contiguous bytes of a row instead of 128.  Every element goes through the additions above
+// whichever way it was loaded, and the output is written one element per thread: the sums depend on (parts, n) alone.
+constexpr int RED_EPB = 128;
+
+__device__ __forceinline__ void reduce_block(const float* __restrict__ part, long part_stride, int parts, long n, long e0,
+                                             float* __restrict__ out, int inner, long s_outer, long s_inner, float (*s_acc)[RED_EPB]) {
+  const int ln = threadIdx.x & 31, pg = threadIdx.x >> 5;
+  const long e = e0 + ln * 4;
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+  if (e + 3 < n && (part_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(part + e) & 15) == 0) {
+    const float* __restrict__ q = part + e;
     int r = pg;
     for (; r + 24 < parts; r += 32) {
-      a0 += part[(long)r * part_stride + e];
-      a1 += part[(long)(r + 8) * part_stride + e];
-      a2 += part[(long)(r + 16) * part_stride + e];
-      a3 += part[(long)(r + 24) * part_stride + e];
+      a0 += *reinterpret_cast<const f32x4*>(q + (long)r * part_stride);
+      a1 += *reinterpret_cast<const f32x4*>(q + (long)(r + 8) * part_stride);
+      a2 += *reinterpret_cast<const f32x4*>(q + (long)(r + 16) * part_stride);
+      a3 += *reinterpret_cast<const f32x4*>(q + (long)(r + 24) * part_stride);
     }
-    for (; r < parts; r += 8) a0 += part[(long)r * part_stride + e];
-  }
-  s_acc[pg][el] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (pg == 0 && e < n) {
-    float t = s_acc[0][el];
+    for (; r < parts; r += 8) a0 += *reinterpret_cast<const f32x4*>(q + (long)r * part_stride);
+  } else {
 #pragma unroll
-    for (int g = 1; g < 8; ++g) t += s_acc[g][el];
-    const long o = (e / inner) * s_outer + (e % inner) * s_inner;
+    for (int k = 0; k < 4; ++k) {
+      if (e + k >= n) break;
+      const float* __restrict__ q = part + e + k;
+      int r = pg;
+      for (; r + 24 < parts; r += 32) {
+        a0[k] += q[(long)r * part_stride];
+        a1[k] += q[(long)(r + 8) * part_stride];
+        a2[k] += q[(long)(r + 16) * part_stride];
+        a3[k] += q[(long)(r + 24) * part_stride];
+      }
+      for (; r < parts; r += 8) a0[k] += q[(long)r * part_stride];
+    }
+  }
+  *reinterpret_cast<f32x4*>(&s_acc[pg][ln * 4]) = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  const long eo = e0 + threadIdx.x;
+  if (threadIdx.x < RED_EPB && eo < n) {
+    float t = s_acc[0][threadIdx.x];
+#pragma unroll
+    for (int g = 1; g < 8; ++g) t += s_acc[g][threadIdx.x];
+    const long o = (eo / inner) * s_outer + (eo % inner) * s_inner;
     out[o] += t;
   }
+}
+
+__global__ __launch_bounds__(256) void k_reduce_parts(const float* __restrict__ part, long part_stride, int parts, long n,
+                                                      float* __restrict__ out, int inner, long s_outer, long s_inner) {
+  __shared__ __attribute__((aligned(16))) float s_acc[8][RED_EPB];
+  reduce_block(part, part_stride, parts, n, (long)blockIdx.x * RED_EPB, out, inner, s_outer, s_inner, s_acc);
 }
 
 // ---- deferred form.  Inside a hipGraph every kernel node costs ~5 us of dispatch however small it is; a training step of the
@@ -57,35 +83,12 @@ struct ReduceBatch {
 };
 
 __global__ __launch_bounds__(256) void k_reduce_batch(const ReduceBatch b) {
-  __shared__ float s_acc[8][32];
+  __shared__ __attribute__((aligned(16))) float s_acc[8][RED_EPB];
   int ji = 0;
   while (ji + 1 < b.njobs && blockIdx.x >= b.j[ji + 1].blk0) ++ji;   // uniform: scalar loads from the kernel arguments
   const ReduceJob& jb = b.j[ji];
-  const float* __restrict__ part = jb.part;
-  const long part_stride = jb.part_stride, n = jb.n;
-  const int parts = jb.parts;
-  const int el = threadIdx.x & 31, pg = threadIdx.x >> 5;
-  const long e = (long)(blockIdx.x - jb.blk0) * 32 + el;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < n) {
-    int r = pg;
-    for (; r + 24 < parts; r += 32) {
-      a0 += part[(long)r * part_stride + e];
-      a1 += part[(long)(r + 8) * part_stride + e];
-      a2 += part[(long)(r + 16) * part_stride + e];
-      a3 += part[(long)(r + 24) * part_stride + e];
-    }
-    for (; r < parts; r += 8) a0 += part[(long)r * part_stride + e];
-  }
-  s_acc[pg][el] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (pg == 0 && e < n) {
-    float t = s_acc[0][el];
-#pragma unroll
-    for (int g = 1; g < 8; ++g) t += s_acc[g][el];
-    const long o = (e / jb.inner) * jb.s_outer + (e % jb.inner) * jb.s_inner;
-    jb.out[o] += t;
-  }
+  reduce_block(jb.part, jb.part_stride, jb.parts, jb.n, (long)(blockIdx.x - jb.blk0) * RED_EPB, jb.out, jb.inner, jb.s_outer, jb.s_inner,
+               s_acc);
 }
 
 static std::mutex g_rj_mu;          // backward runs on autograd's device thread, the flush on the caller's
@@ -118,7 +121,7 @@ static int flush_jobs_locked(hipStream_t st) {
       if (clash) break;
       ReduceJob j = g_rj[i++];
       j.blk0 = blk;
-      blk += (unsigned)((j.n + 31) / 32);
+      blk += (unsigned)((j.n + RED_EPB - 1) / RED_EPB);
       b.j[b.njobs++] = j;
     }
     hipLaunchKernelGGL(k_reduce_batch, dim3(blk), dim3(256), 0, st, b);
@@ -139,7 +142,7 @@ int reduce_parts(const float* part, long part_stride, int parts, long n, float* 
       return 0;
     }
   }
-  const long blocks = (n + 31) / 32;
+  const long blocks = (n + RED_EPB - 1) / RED_EPB;
   hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)blocks), dim3(256), 0, st, part, part_stride, parts, n, out, inner, s_outer,
                      s_inner);
   return check_launch("reduce_parts");
