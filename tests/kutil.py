@@ -41,10 +41,11 @@ def tol(dtype):
 
 
 # ---- depthwise kernel tests (tests/test_dwconv_family_gpu.py)
-def fresh(M, C, dtype):
-    """output buffer as the allocator hands it out: padding channels zero, the valid region poisoned (unwritten elements are caught)"""
-    b = torch.zeros(M, pad8(C), dtype=dtype, device="cuda")
-    b[:, :C] = 7.0
+def fresh(M, C, dtype, poison=7.0, device="cuda"):
+    """output buffer as the allocator hands it out: padding channels zero, the valid region poisoned (unwritten elements are caught;
+    tests whose references are integers pass a NaN poison, which equals no reference value)"""
+    b = torch.zeros(M, pad8(C), dtype=dtype, device=device)
+    b[:, :C] = poison
     return b
 
 

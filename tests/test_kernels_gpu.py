@@ -141,6 +141,10 @@ GEMM_SHAPES = [(100, 24, 16), (1000, 432, 24), (333, 40, 139), (64, 16, 432), (2
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
 @pytest.mark.parametrize("variant", ["plain_stats", "bnrelu_stats", "bnbwd_mask_statz", "bnbwd_add_statz", "bias_f32", "plain_mask_statz"])
 def test_gemm_nt(gpu_lib, dtype, M, N, K, variant):
+    """Random operands against float64.  The bounds below are ROUNDING bounds (one bf16 output rounding scaled by max|C|; sqrt(M) for
+    the statistics): a single product a*w or a single row's share of a statistic is smaller than they are, so they do not account for
+    terms.  Term accounting (a dropped or doubled k-element or row, a mask decided at its bound) lives in tests/test_pw_exact_gpu.py,
+    whose integer cases are compared with tolerance zero."""
     ops = _ops()
     g = torch.Generator().manual_seed(M + 7 * N + 13 * K)
     r = lambda *s: torch.randn(*s, generator=g)
