@@ -40,6 +40,7 @@ SIGNATURES = {
     "atomnas_se_bwd_apply": [vp, i32, i64, vp, i32, i64, vp, vp, i32, vp, vp, i32, vp, i32, i64, vp, i32, i64, i32, i32, i32, vp],
     "atomnas_im2col_stem": [vp, vp, i32, i32, i32, i32, i32, vp],
     "atomnas_ce_smooth": [vp, i32, vp, f32, i32, i32, vp, vp, i32, f32, vp, i32, vp],
+    "atomnas_ce_distill": [vp, i32, vp, i32, vp, f32, f32, f32, i32, i32, vp, vp, vp, i32, f32, vp, i32, vp],
     "atomnas_colsum": [vp, i32, vp, i64, i32, i32, vp],
     "atomnas_fused_rmsprop_ema": [vp, vp, vp, vp, vp, vp, i64, vp, f64, f64, i32, f64, vp, vp, vp],
     "atomnas_fused_sgd_ema": [vp, vp, vp, vp, vp, i64, vp, f64, i32, vp, vp, vp],

@@ -96,6 +96,107 @@ __global__ __launch_bounds__(256) void k_ce_smooth(const float* __restrict__ log
   }
 }
 
+// ---- knowledge distillation: the same loss with a soft-target term from a frozen teacher
+// z_j = x_j / T of one row, and log softmax(x / T)_j = z_j - lse.  Contraction is switched off in both: the student's and the teacher's
+// rows go through the SAME rounded operations, so that two rows of equal bits give equal bits whatever the compiler would fuse around
+// either call (k_ce_distill's second exactness property rests on it).
+__device__ __forceinline__ float soft_z(float x, float invT) {
+#pragma clang fp contract(off)
+  return x * invT;
+}
+__device__ __forceinline__ float soft_logp(float x, float invT, float lse) {
+#pragma clang fp contract(off)
+  const float z = x * invT;
+  return z - lse;
+}
+// log sum_j exp(x_j / T) of one row over a wave, with its own max subtraction; lanes sum in steps of 64, then the fixed xor tree
+__device__ __forceinline__ float wave_lse_t(const float* __restrict__ x, int K, float invT, int lane) {
+  float mx = -INFINITY;
+  for (int j = lane; j < K; j += 64) mx = fmaxf(mx, soft_z(x[j], invT));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float se = 0.f;
+  for (int j = lane; j < K; j += 64) se += expf(soft_logp(x[j], invT, mx));
+  se = wave_sum(se);
+  return mx + logf(se);
+}
+
+// One wave per sample, as k_ce_smooth.  With p = softmax(s), pT = softmax(s / T), q = softmax(t / T) (s the student's row, t the teacher's):
+//   kd_i = T^2 * sum_j q_j * (log q_j - log pT_j);   loss_i = (1 - alpha) * CE_smooth_i + alpha * kd_i
+//   dlogits_j = [(1 - alpha) * (p_j - tgt_j) + alpha * T * (pT_j - q_j)] * gscale / B
+// The CE part is k_ce_smooth's code, expression by expression and in its order: with alpha == 0 the combination multiplies it by 1 and adds
+// a zero, so loss, dlogits and the hit counts carry k_ce_smooth's bits.  log q_j and log pT_j are z_j - lse (never the logarithm of a
+// probability): a class whose q_j underflows contributes 0 * finite = 0.  top-k reads the student's row and the hard label only.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ce_distill(const float* __restrict__ logits, int ldl, const float* __restrict__ teacher, int ldt,
+                                                    const long long* __restrict__ target, float eps, float alpha, float temperature, int B,
+                                                    int K, float* __restrict__ loss_per_sample, float* __restrict__ kd_per_sample,
+                                                    T* __restrict__ dlogits, int ldd, float gscale,
+                                                    int* __restrict__ topk_correct /*[2]: top1, top5*/) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* x = logits + (long)b * ldl;
+  const float* tx = teacher + (long)b * ldt;
+  const int y = (int)target[b];
+  // hard-label part (k_ce_smooth)
+  float mx = -INFINITY;
+  for (int j = lane; j < K; j += 64) mx = fmaxf(mx, x[j]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float se = 0.f, sx = 0.f;
+  const float xy = x[y];
+  int rank = 0;
+  for (int j = lane; j < K; j += 64) {
+    const float v = x[j];
+    se += expf(v - mx);
+    sx += v;
+    rank += (v > xy) ? 1 : 0;
+  }
+  se = wave_sum(se);
+  sx = wave_sum(sx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+  const float lse = mx + logf(se);
+  const float ce = -(1.f - eps) * (xy - lse) - (eps / (float)K) * (sx - (float)K * lse);
+  // soft-target part
+  const float invT = 1.f / temperature;
+  const float lse_p = wave_lse_t(x, K, invT, lane);
+  const float lse_q = wave_lse_t(tx, K, invT, lane);
+  float kd = 0.f;
+  for (int j = lane; j < K; j += 64) {
+    const float lq = soft_logp(tx[j], invT, lse_q);
+    const float lp = soft_logp(x[j], invT, lse_p);
+    kd += expf(lq) * (lq - lp);
+  }
+  kd = wave_sum(kd) * (temperature * temperature);
+  const float wce = 1.f - alpha;
+  if (lane == 0) {
+    if (loss_per_sample) loss_per_sample[b] = wce * ce + alpha * kd;
+    if (kd_per_sample) kd_per_sample[b] = kd;
+    if (topk_correct) {   // integer atomics: exact and order-independent
+      if (rank < 1) atomicAdd(&topk_correct[0], 1);
+      if (rank < 5) atomicAdd(&topk_correct[1], 1);
+    }
+  }
+  if (dlogits) {
+    T* d = dlogits + (long)b * ldd;
+    const float invB = gscale / (float)B;
+    const float wkd = alpha * temperature;
+    for (int j = lane; j < ldd; j += 64) {
+      float g = 0.f;
+      if (j < K) {
+        const float p = expf(x[j] - lse);
+        const float t = eps / (float)K + ((j == y) ? (1.f - eps) : 0.f);
+        const float pt = expf(soft_logp(x[j], invT, lse_p));
+        const float q = expf(soft_logp(tx[j], invT, lse_q));
+        g = (wce * (p - t) + wkd * (pt - q)) * invB;
+      }
+      d[j] = from_f32<T>(g);
+    }
+  }
+}
+
 // column sums of a [M, C] tensor of storage type T into fp32 (classifier bias gradient): one thread per column, rows in
 // order (M is the batch size here), so the result is bit-reproducible
 template <typename T>
@@ -144,6 +245,23 @@ extern "C" int atomnas_ce_smooth(const float* logits, int ldl, const long long* 
     hipLaunchKernelGGL(k_ce_smooth<bf16_t>, dim3((B + 3) / 4), dim3(256), 0, st, logits, ldl, target, eps, B, K, loss_per_sample,
                        (bf16_t*)dlogits, ldd, gscale, topk_correct);
   return check_launch("ce_smooth");
+}
+
+extern "C" int atomnas_ce_distill(const float* logits, int ldl, const float* teacher, int ldt, const long long* target, float eps,
+                                  float alpha, float temperature, int B, int K, float* loss_per_sample, float* kd_per_sample,
+                                  void* dlogits, int ldd, float gscale, int* topk_correct, int dtype, void* stream) {
+  ATOMNAS_REQUIRE(logits && teacher && target && B > 0 && K > 0 && ldl >= K && ldt >= K, "ce_distill: bad arguments");
+  ATOMNAS_REQUIRE(!dlogits || ldd >= K, "ce_distill: bad gradient pitch");
+  ATOMNAS_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "ce_distill: the temperature must be positive and finite");   // NaN fails too
+  ATOMNAS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "ce_distill: alpha must lie in [0, 1]");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(k_ce_distill<float>, dim3((B + 3) / 4), dim3(256), 0, st, logits, ldl, teacher, ldt, target, eps, alpha, temperature,
+                       B, K, loss_per_sample, kd_per_sample, (float*)dlogits, ldd, gscale, topk_correct);
+  else
+    hipLaunchKernelGGL(k_ce_distill<bf16_t>, dim3((B + 3) / 4), dim3(256), 0, st, logits, ldl, teacher, ldt, target, eps, alpha,
+                       temperature, B, K, loss_per_sample, kd_per_sample, (bf16_t*)dlogits, ldd, gscale, topk_correct);
+  return check_launch("ce_distill");
 }
 
 extern "C" int atomnas_colsum(const void* x, int ld, float* out, long M, int C, int dtype, void* stream) {

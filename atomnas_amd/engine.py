@@ -27,6 +27,12 @@ torch optimizer's weight_decay stays outside clip_grad_norm_), and a one-workgro
 gradient scale hyper[HYP_GRAD_SCALE] * clip coefficient, norm, coefficient, two cumulative counters.  The guarded optimizer launch scales
 by it, or, with OK = 0 (non-finite gradients), writes nothing; the BatchNorm running statistics, which the forward pass has already
 overwritten, then go back to their values of the start of the step, and their EMA is left alone.  Nothing synchronises with the host.
+
+Knowledge distillation (teacher=; None, the default: nothing of it is allocated, captured or launched).  A frozen second model of this
+project runs its eval forward on the step's images in front of the student's forward, inside _fwd_bwd and therefore inside every step
+form and every captured graph; its classifier writes into the static buffer teacher_logits, and the loss node computes
+(1 - alpha) * CE_smooth + alpha * T^2 * KL(softmax(teacher / T) || softmax(student / T)) and its gradient in one launch
+(atomnas_ce_distill).  loss[0] is the mean of that objective, kd the mean of its unweighted soft term.
 """
 import os
 
@@ -54,17 +60,38 @@ def check_clip_norm(clip_norm):
     return float(clip_norm) if clip_norm else None
 
 
+def check_teacher(model, teacher, alpha, temperature):
+    """TrainStep's distillation arguments -> (alpha, temperature) as floats; ValueError for values outside 0 <= alpha <= 1, 0 < T < inf,
+    alpha > 0 without a teacher, a teacher that is the student, one with another class count or on another device"""
+    alpha, temperature = aopt.check_distill(alpha, temperature)
+    if teacher is None:
+        if alpha > 0.0:
+            raise ValueError("distill_alpha = %r needs a teacher" % alpha)
+        return alpha, temperature
+    if teacher is model:
+        raise ValueError("the teacher is the student object: distilling a network from itself is not supported")
+    ks, kt = getattr(model, "num_classes", None), getattr(teacher, "num_classes", None)
+    if ks is None or kt is None or ks != kt:
+        raise ValueError("the teacher classifies %r classes, the student %r" % (kt, ks))
+    ds, dt = next(model.parameters()).device, next(teacher.parameters()).device
+    if ds != dt:
+        raise ValueError("the teacher is on %s, the student on %s" % (dt, ds))
+    return alpha, temperature
+
+
 class TrainStep:
 
     def __init__(self, model, optimizer, ema=None, prune_info=None, weight_decay=1e-5, wd_method='mnas', label_smoothing=0.1,
                  batch_size=256, image_size=224, use_graph=True, process_group=None, world_size=1, allreduce_bn=False, accum_steps=1,
-                 clip_norm=None, skip_nonfinite=False):
+                 clip_norm=None, skip_nonfinite=False, teacher=None, distill_alpha=0.0, distill_temperature=1.0):
         """clip_norm: maximal global L2 norm of the gradient the optimizer consumes (torch.nn.utils.clip_grad_norm_; None or 0: no
         clipping).  skip_nonfinite: a step whose gradient arena holds a NaN or an Inf is dropped on the device (GradScaler-style): P, the
         optimizer state, both EMAs and the BN running statistics keep their values of before the step.  What a dropped step still
         advances, as GradScaler + a scheduler do: global_step, ema.note_updates (the EMA warm-up count), the learning-rate and rho
         schedules of the caller, the dropout counter and num_batches_tracked of every BatchNorm.  guard_state() reads the verdict."""
         self.clip_norm = check_clip_norm(clip_norm)   # first: a bad value is refused before any device work
+        self.distill_alpha, self.distill_temperature = check_teacher(model, teacher, distill_alpha, distill_temperature)
+        self.teacher = teacher
         self.model, self.optimizer, self.ema, self.prune_info = model, optimizer, ema, prune_info
         self.weight_decay, self.wd_method = weight_decay, wd_method
         self.use_graph = use_graph
@@ -87,6 +114,21 @@ class TrainStep:
         self.loss = self._scal[0:3]                                    # CE (mean), L2, L1 of the last step
         self.topk = self._scal[4:6].view(torch.int32)                  # top-1 / top-5 hits of the last step (common.py:73-79)
         self.loss_vec = torch.zeros(batch_size, dtype=torch.float32, device=dev)   # per-sample CE of the last step
+        # knowledge distillation (teacher None, the default: nothing below is allocated, captured or launched).  The teacher is frozen: eval
+        # mode, no gradients, arenas of its own; the optimizer, the EMA, the prune table, a shrink, the collectives and a checkpoint never
+        # see it (they are all built from `model`).  With several ranks every rank holds its own copy.
+        self.kd = self.kd_vec = self.teacher_logits = self._teacher_out = self._distill = None
+        if teacher is not None:
+            teacher.eval()
+            for p in teacher.parameters():
+                p.requires_grad_(False)
+            runtime.manager_of(teacher).ensure()   # before any capture
+            K = int(model.num_classes)
+            self._teacher_out = torch.zeros(batch_size, ops.pad8(K), dtype=torch.float32, device=dev)   # the teacher's classifier writes here
+            self.teacher_logits = self._teacher_out[:, :K]
+            self.kd = self._scal[3:4]                                              # mean of kd_vec, cleared with the other scalars
+            self.kd_vec = torch.zeros(batch_size, dtype=torch.float32, device=dev)   # per-sample T^2 * KL(teacher || student)
+            self._distill = (self.teacher_logits, self.distill_alpha, self.distill_temperature, self.kd_vec, self.kd)
         self._tables_version = -1
         self._comm = None          # side stream of the bucketed all-reduce
         self._buckets = []         # (first plan of the bucket, lo, hi) in backward order
@@ -238,9 +280,17 @@ class TrainStep:
         # up over the micro-batches), and the BatchNorm counters advance with the last micro-batch only
         if last is None:
             ops.zero_(self._scal)
+        loss_args = (self.y, self.label_smoothing, self.loss_vec, self.topk, self.loss[0:1])
+        if self.teacher is not None:
+            # the frozen teacher's eval forward on the same images, part of the same graph; it moves nothing of the teacher's state
+            if self.teacher.training:
+                self.teacher.eval()
+            with torch.no_grad():
+                self.teacher(self.x, logits_out=self._teacher_out)
+            loss_args += (self._distill,)
         mgr.hold_counters = last is False
         try:
-            loss = self.model(self.x, loss_args=(self.y, self.label_smoothing, self.loss_vec, self.topk, self.loss[0:1]))
+            loss = self.model(self.x, loss_args=loss_args)
         finally:
             mgr.hold_counters = False
         if self._seed_grad is None or self._seed_grad.shape != loss.shape:
@@ -257,7 +307,10 @@ class TrainStep:
             if not self._fold_buckets:   # G -> running sum; after the last micro-batch G holds the sum in micro-batch order
                 ops.accum_fold(self._acc, mgr.G, None, nP, False, last)
             # CE mean -> running sum behind the gradients'; after the last micro-batch loss[0] is the mean of the micro-batch means
-            ops.accum_fold(self._acc[nP:], self.loss, None, 1, False, last, 1.0 / self.accum_steps)
+            # distilling: the four leading scalars in the same launch -- kd sits in _scal[3], and _scal[1:3] (L2, L1) are still zero here
+            # (_opt writes them after the last fold)
+            ops.accum_fold(self._acc[nP:], self._scal if self.teacher is not None else self.loss, None, 4 if self.teacher is not None else 1,
+                           False, last, 1.0 / self.accum_steps)
             if not last:
                 ops.add_i64(mgr.step_counter, 1)   # every micro-batch draws its own dropout masks (the last one's advance is in _opt)
 

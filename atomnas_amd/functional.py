@@ -659,8 +659,9 @@ def run_convbn(pl, x, anchor):
 
 
 # ---------------------------------------------------------------------------------------------- fused tail: last conv + pool + dropout + fc
-def tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, need_grad):
-    """features[-2] (1x1 ConvBNReLU) -> AvgPool2d(H) -> squeeze -> Dropout -> Linear, without materialising the activated map."""
+def tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, need_grad, logits_out=None):
+    """features[-2] (1x1 ConvBNReLU) -> AvgPool2d(H) -> squeeze -> Dropout -> Linear, without materialising the activated map.
+    logits_out: fp32 [N, pad8(classes)] buffer of the caller that receives the logits (the static buffer of a frozen teacher)."""
     mgr = lp.mgr
     T = mgr.compute_dtype
     dev = x.device
@@ -680,7 +681,11 @@ def tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, need_grad):
         TAIL_TAP.append(keep)
     ops.bn_act_pool(L, b.scale, b.shift, int(act), pooled, keep, p, seed, step_ptr, N, H * W, lp.cout)
     Kc = fp.cout
-    logits = torch.empty(N, pad8(Kc), dtype=torch.float32, device=dev)
+    logits = logits_out
+    if logits is None:
+        logits = torch.empty(N, pad8(Kc), dtype=torch.float32, device=dev)
+    elif tuple(logits.shape) != (N, pad8(Kc)) or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits_out must be a contiguous fp32 [%d, %d] tensor" % (N, pad8(Kc)))
     ops.gemm_nt(pooled, fp.W_pack, logits, N, Kc, fp.cin, bias=fp.bias)
     _stap(lp, L=L, bn=b, pooled=pooled, logits=logits[:, :Kc])
     sv = None
@@ -741,10 +746,12 @@ class TailFunction(torch.autograd.Function):
         return to_4d(gx, N, H, W, lp.cin), None, None, None, None, None, None, None
 
 
-def run_tail(lp, fp, x, anchor, drop_p, training, seed, step_ptr):
+def run_tail(lp, fp, x, anchor, drop_p, training, seed, step_ptr, logits_out=None):
     if torch.is_grad_enabled() and (x.requires_grad or anchor.requires_grad):
+        if logits_out is not None:
+            raise ValueError("logits_out is for forwards without a gradient (torch.no_grad())")
         return TailFunction.apply(x, anchor, lp, fp, drop_p, training, seed, step_ptr)
-    logits, _ = tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, False)
+    logits, _ = tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, False, logits_out)
     return logits
 
 
@@ -753,16 +760,29 @@ class TailLossFunction(torch.autograd.Function):
     autograd node for engine.TrainStep: the loss kernel writes d(mean loss)/d(logits) directly in the compute dtype with zeroed
     padding, so no ATen op (mean, its backward, dtype / padding copies) is left between the HIP launches
     (train.py:176-180 `loss = forward_loss(...)`, utils/optim.py:199-207, common.py:67-80).
-    Returns the scalar mean loss; loss_vec / topk receive the per-sample losses and the top-1 / top-5 hit counts."""
+    Returns the scalar mean loss; loss_vec / topk receive the per-sample losses and the top-1 / top-5 hit counts.
+    distill = (teacher_logits, alpha, temperature, kd_vec, kd_out), optional: the loss becomes (1 - alpha) * CE + alpha * T^2 *
+    KL(teacher || student) in one launch (atomnas_ce_distill); without it the node issues exactly what it issued before."""
 
     @staticmethod
-    def forward(ctx, x, anchor, lp, fp, drop_p, training, seed, step_ptr, target, eps, loss_vec, topk, loss_out):
+    def forward(ctx, x, anchor, lp, fp, drop_p, training, seed, step_ptr, target, eps, loss_vec, topk, loss_out, distill=None):
         logits, sv = tail_forward(lp, fp, x, drop_p, training, seed, step_ptr, True)
         B, K = logits.shape
         T = lp.mgr.compute_dtype
         dl = torch.empty(B, pad8(K), dtype=T, device=x.device)
-        ops.ce_smooth(logits, target, eps, B, K, loss_vec, dl, 1.0, topk)   # gscale 1: dl = d(mean loss)/d(logits)
-        ops.vec_sum(loss_vec, B, 1.0 / B, loss_out)
+        if distill is None:
+            ops.ce_smooth(logits, target, eps, B, K, loss_vec, dl, 1.0, topk)   # gscale 1: dl = d(mean loss)/d(logits)
+            ops.vec_sum(loss_vec, B, 1.0 / B, loss_out)
+        else:
+            # knowledge distillation: the combined objective (1 - alpha) * CE + alpha * T^2 * KL(teacher || student) is what loss_vec,
+            # loss_out and dl carry; kd_vec / kd_out receive the unweighted second term and its mean
+            teacher_logits, alpha, temperature, kd_vec, kd_out = distill
+            if tuple(teacher_logits.shape) != (B, K):
+                raise ValueError("teacher logits are %s, the student's %s" % (tuple(teacher_logits.shape), (B, K)))
+            ops.ce_distill(logits, teacher_logits, target, eps, alpha, temperature, B, K, loss_vec, kd_vec, dl, 1.0, topk)
+            ops.vec_sum(loss_vec, B, 1.0 / B, loss_out)
+            ops.vec_sum(kd_vec, B, 1.0 / B, kd_out)
+        ctx.n_in = 13 if distill is None else 14
         ctx.lp, ctx.fp, ctx.sv, ctx.dl = lp, fp, sv, dl
         ctx.logits = logits
         return loss_out[0]
@@ -782,7 +802,7 @@ class TailLossFunction(torch.autograd.Function):
         lp.mgr.grad_done(fp)
         lp.mgr.grad_done(lp)
         N, H, W = sv["dims"]
-        return (to_4d(gx, N, H, W, lp.cin),) + (None,) * 12
+        return (to_4d(gx, N, H, W, lp.cin),) + (None,) * (ctx.n_in - 1)
 
 
 # ---------------------------------------------------------------------------------------------- loss
@@ -808,3 +828,30 @@ class CESmoothFunction(torch.autograd.Function):
     def backward(ctx, gout):
         (dl,) = ctx.saved_tensors
         return dl * gout.unsqueeze(1), None, None, None
+
+
+class CEDistillFunction(torch.autograd.Function):
+    """Per-sample (1 - alpha) * label-smoothed CE + alpha * T^2 * KL(softmax(teacher / T) || softmax(logits / T)); leaves the hit counts
+    in `topk` as CESmoothFunction does and the unweighted second term in `kd` (fp32 [B]).  The teacher's logits get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher, target, eps, alpha, temperature, topk, kd):
+        if not (logits.is_cuda and teacher.is_cuda):
+            raise ops._lib.AtomnasHipError("DistillCrossEntropy runs on the GPU only")
+        B, K = logits.shape
+        lg, tc = logits.float(), teacher.float()
+        if lg.stride(1) != 1:
+            lg = lg.contiguous()
+        if tc.stride(1) != 1:
+            tc = tc.contiguous()
+        loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+        dl = torch.empty(B, K, dtype=torch.float32, device=logits.device)
+        # gscale = B: dl holds d(loss_i)/d(logits_i) (the 1/B of a mean reduction comes in through grad_output)
+        ops.ce_distill(lg, tc, target, eps, alpha, temperature, B, K, loss, kd, dl, float(B), topk)
+        ctx.save_for_backward(dl)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dl,) = ctx.saved_tensors
+        return (dl * gout.unsqueeze(1),) + (None,) * 7

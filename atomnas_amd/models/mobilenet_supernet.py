@@ -77,9 +77,12 @@ class _HipModel(nn.Module):
         self.drop_connect_rate = rate
         return self
 
-    def forward(self, x, loss_args=None):
+    def forward(self, x, loss_args=None, logits_out=None):
         """loss_args (engine.TrainStep only): (target, label_smoothing, loss_vec, topk, loss_out) -- the tail and the
-        label-smoothed cross entropy then run as one autograd node and the scalar mean loss is returned instead of the logits."""
+        label-smoothed cross entropy then run as one autograd node and the scalar mean loss is returned instead of the logits.
+        An optional sixth element distill = (teacher_logits, alpha, temperature, kd_vec, kd_out) adds the soft-target term of
+        knowledge distillation (functional.TailLossFunction).
+        logits_out (forwards under torch.no_grad() only): fp32 [N, pad8(num_classes)] buffer the classifier writes the logits into."""
         if not x.is_cuda:
             raise AF.ops._lib.AtomnasHipError('this model runs on the GPU through libatomnas_hip.so only (input is on %s)' % x.device)
         mgr = runtime.manager_of(self)
@@ -95,12 +98,14 @@ class _HipModel(nn.Module):
             if not (isinstance(last, ConvBNReLU) and isinstance(pool, nn.AvgPool2d) and y.shape[2] == k and y.shape[3] == k):
                 raise NotImplementedError('the tail must be 1x1 ConvBNReLU -> global AvgPool2d -> Dropout -> Linear')
             if loss_args is not None:
-                target, eps, loss_vec, topk, loss_out = loss_args
-                return AF.TailLossFunction.apply(y, mgr.anchor, runtime.plan_of(last), runtime.plan_of(fc), drop.p,
-                                                 self.training and drop.training, self.dropout_seed, mgr.step_counter, target,
-                                                 float(eps), loss_vec, topk, loss_out)
+                target, eps, loss_vec, topk, loss_out = loss_args[:5]
+                targs = (y, mgr.anchor, runtime.plan_of(last), runtime.plan_of(fc), drop.p, self.training and drop.training,
+                         self.dropout_seed, mgr.step_counter, target, float(eps), loss_vec, topk, loss_out)
+                if len(loss_args) > 5 and loss_args[5] is not None:   # distill: the soft-target loss instead
+                    targs += (loss_args[5],)
+                return AF.TailLossFunction.apply(*targs)
             return AF.run_tail(runtime.plan_of(last), runtime.plan_of(fc), y, mgr.anchor, drop.p, self.training and drop.training,
-                               self.dropout_seed, mgr.step_counter)
+                               self.dropout_seed, mgr.step_counter, logits_out)
         finally:
             mgr.leave()
 

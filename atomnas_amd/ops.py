@@ -533,6 +533,17 @@ def ce_smooth(logits, target, eps, B, K, loss_per_sample, dlogits, gscale, topk)
          dt_code(dlogits.dtype) if dlogits is not None else 0, _stream())
 
 
+def ce_distill(logits, teacher, target, eps, alpha, temperature, B, K, loss_per_sample, kd_per_sample, dlogits, gscale, topk):
+    """ce_smooth with a soft-target term: loss = (1 - alpha) * CE_smooth + alpha * T^2 * KL(softmax(teacher / T) || softmax(logits / T)),
+    kd_per_sample the unweighted second term"""
+    assert logits.dtype == torch.float32 and teacher.dtype == torch.float32 and target.dtype == torch.int64
+    _rec("ce_distill", B=int(B), K=int(K), ldl=_lay(logits), ldt=_lay(teacher), dl=_lay(dlogits),
+         dt=dt_code(dlogits.dtype) if dlogits is not None else 0)
+    call("atomnas_ce_distill", _p(logits), _ld(logits), _p(teacher), _ld(teacher), _p(target), float(eps), float(alpha), float(temperature),
+         B, K, _p(loss_per_sample), _p(kd_per_sample), _p(dlogits), _ld(dlogits) if dlogits is not None else 0, float(gscale), _p(topk),
+         dt_code(dlogits.dtype) if dlogits is not None else 0, _stream())
+
+
 def colsum(x, out, M, C):
     _rec("colsum", M=int(M), C=int(C), x=_lay(x), dt=dt_code(x.dtype))
     call("atomnas_colsum", _p(x), _ld(x), _p(out), M, C, dt_code(x.dtype), _stream())

@@ -30,6 +30,50 @@ class CrossEntropyLabelSmooth(nn.Module):
         return loss
 
 
+def check_distill(alpha, temperature):
+    """alpha, temperature of a distillation loss -> (float, float); ValueError outside 0 <= alpha <= 1, 0 < T < inf (NaN included)"""
+    for name, v in (('alpha', alpha), ('temperature', temperature)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError('distill {} must be a number, got {!r}'.format(name, v))
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError('distill alpha must lie in [0, 1], got {!r}'.format(alpha))
+    if not 0.0 < temperature < float('inf'):
+        raise ValueError('distill temperature must be positive and finite, got {!r}'.format(temperature))
+    return float(alpha), float(temperature)
+
+
+class DistillCrossEntropy(nn.Module):
+    """Knowledge distillation for eager use outside engine.TrainStep: per sample
+    (1 - alpha) * label-smoothed CE + alpha * T^2 * KL(softmax(teacher / T) || softmax(student / T)), one launch.  The teacher's
+    logits receive no gradient.  `topk_correct` (int32[2]) counts the student's top-1 / top-5 hits as CrossEntropyLabelSmooth does;
+    `kd` holds the unweighted per-sample second term of the last call."""
+
+    def __init__(self, num_classes, label_smoothing, alpha, temperature, reduction='none'):
+        super().__init__()
+        self.num_classes, self.label_smoothing = num_classes, label_smoothing
+        self.alpha, self.temperature = check_distill(alpha, temperature)
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError('Unknown reduction: {}'.format(reduction))
+        self.reduction = reduction
+        self.topk_correct = None
+        self.kd = None
+
+    def forward(self, inputs, teacher_logits, targets):
+        assert inputs.size(1) == self.num_classes
+        if teacher_logits.shape != inputs.shape:
+            raise ValueError('teacher logits are {}, the student\'s {}'.format(tuple(teacher_logits.shape), tuple(inputs.shape)))
+        if self.topk_correct is None or self.topk_correct.device != inputs.device:
+            self.topk_correct = torch.zeros(2, dtype=torch.int32, device=inputs.device)
+        self.kd = torch.empty(inputs.size(0), dtype=torch.float32, device=inputs.device)
+        loss = AF.CEDistillFunction.apply(inputs, teacher_logits.detach(), targets, float(self.label_smoothing), self.alpha,
+                                          self.temperature, self.topk_correct, self.kd)
+        if self.reduction == 'mean':
+            return loss.mean()
+        if self.reduction == 'sum':
+            return loss.sum()
+        return loss
+
+
 # ---------------------------------------------------------------------------------------------- L2 regulariser
 class _RegFunction(torch.autograd.Function):
     """Scalar regulariser over an arena job table: value in forward, gradient contribution added to the gradient arena in

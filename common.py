@@ -167,6 +167,88 @@ def guard_options():
     return (float(c) if c else None), s
 
 
+DISTILL_KEYS = ('model', 'model_kwparams', 'checkpoint', 'alpha', 'temperature')
+
+
+def distill_options():
+    """the yaml's `distill:` block -> None (absent: off) or dict(model=, model_kwparams=, checkpoint=, alpha=, temperature=).
+    model defaults to the run's own `model`, alpha to 0.5, temperature to 1; keys of the form 'model_kwparams.x' override entries of
+    model_kwparams, as dotted keys do at the top level of a yaml.  Unknown keys, a missing architecture, alpha outside [0, 1], a
+    temperature that is not positive and finite and a class count other than the student's are ValueErrors."""
+    d = FLAGS.get('distill', None)
+    if d is None:
+        return None
+    if not isinstance(d, dict):
+        raise ValueError('distill must be a mapping (model, model_kwparams, checkpoint, alpha, temperature), got {!r}'.format(d))
+    d = dict(d)
+    dotted = [k for k in d if isinstance(k, str) and '.' in k]
+    plain = {k: v for k, v in d.items() if k not in dotted}
+    unknown = sorted(str(k) for k in plain if k not in DISTILL_KEYS)
+    if unknown:
+        raise ValueError('unknown distill key(s) {}: the block takes {}'.format(', '.join(unknown), ', '.join(DISTILL_KEYS)))
+    kw = plain.get('model_kwparams', None)
+    if not isinstance(kw, dict):
+        raise ValueError('distill.model_kwparams must be the teacher\'s architecture (a mapping, e.g. `!include best_model.yml`), got {!r}'
+                         .format(kw))
+    kw = copy.deepcopy(dict(kw))
+    for k in dotted:
+        parts = k.split('.')
+        if parts[0] != 'model_kwparams' or len(parts) < 2:
+            raise ValueError('distill override {!r}: only model_kwparams.<name> can be overridden'.format(k))
+        node = kw
+        for part in parts[1:-1]:
+            node = node[part]
+        node[parts[-1]] = d[k]
+    alpha, temperature = optim.check_distill(plain.get('alpha', 0.5), plain.get('temperature', 1.0))
+    classes, own = kw.get('num_classes', 1000), FLAGS.model_kwparams.get('num_classes', 1000)
+    if classes != own:
+        raise ValueError('the distill teacher classifies {} classes, the model {}'.format(classes, own))
+    ckpt = plain.get('checkpoint', None)
+    if ckpt is not None and not isinstance(ckpt, str):
+        raise ValueError('distill.checkpoint must be a file name, got {!r}'.format(ckpt))
+    return dict(model=plain.get('model', None) or FLAGS.model, model_kwparams=kw, checkpoint=ckpt, alpha=alpha, temperature=temperature)
+
+
+def teacher_state_dict(ckpt):
+    """What a teacher loads from a checkpoint file's content: the EMA weights and statistics where the file carries an EMA (they are what
+    a run validates and what best_model.pt is chosen by), over the model's own entries for everything the EMA does not track
+    (num_batches_tracked); a bare state_dict as it is.  Keys lose a wrapper's `module.` prefix."""
+    from atomnas_amd.utils.common import unwrap_state_dict
+    if not (isinstance(ckpt, dict) and 'model' in ckpt):
+        return unwrap_state_dict(ckpt, verbose=False)
+    sd = dict(unwrap_state_dict(ckpt['model'], verbose=False))
+    ema = ckpt.get('ema')
+    if ema:
+        shadow = dict(ema.get('shadow') or {})
+        for name, v in unwrap_state_dict(shadow, verbose=False).items():
+            if name in sd:
+                sd[name] = v
+    return sd
+
+
+def get_teacher():
+    """The frozen teacher of a distilling run (`distill:`), or None: built with the run's image_size and compute_dtype, loaded from
+    distill.checkpoint, on the device, in eval mode.  distill_options() holds its alpha and temperature."""
+    opts = distill_options()
+    if opts is None:
+        return None
+    model_lib = importlib.import_module(opts['model'])
+    teacher = model_lib.Model(**opts['model_kwparams'], input_size=FLAGS.image_size)
+    if FLAGS.get('compute_dtype', 'bf16') == 'f32':
+        teacher.set_compute_dtype(torch.float32)
+    if opts['checkpoint']:
+        ckpt = torch.load(opts['checkpoint'], map_location='cpu', weights_only=False)
+        teacher.load_state_dict(teacher_state_dict(ckpt))
+        logging.info('Loaded distill teacher {}.'.format(opts['checkpoint']))
+    else:
+        logging.warning('distill: no checkpoint, the teacher keeps its initial weights')
+    teacher.cuda()
+    teacher.eval()
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    return teacher
+
+
 def all_steps_skipped(skipped_before, skipped_now, steps):
     """The abort rule of a guarded run: True when `steps` > 0 optimizer steps ran since the counter read `skipped_before` and every one
     of them was dropped (the cumulative counter of engine.TrainStep.guard_state() advanced by all of them).  One dropped step among good

@@ -265,6 +265,18 @@ int atomnas_im2col_stem(const float* img, void* col, int ld, int N, int H, int W
  * dlogits = d(mean loss)/dlogits * gscale, storage dtype, columns K..ldd-1 zeroed. */
 int atomnas_ce_smooth(const float* logits, int ldl, const long long* target, float eps, int B, int K, float* loss_per_sample,
                       void* dlogits, int ldd, float gscale, int* topk_correct, int dtype, void* stream);
+/* The same loss with a soft-target term from a frozen teacher (knowledge distillation; added within ABI 9: a new symbol, nothing existing
+ * changes).  With p = softmax(s), pT = softmax(s / T), q = softmax(t / T), s a row of logits, t the row of teacher, T = temperature > 0,
+ * 0 <= alpha <= 1:
+ *   kd_i      = T^2 * sum_j q_j * (log q_j - log pT_j)            -> kd_per_sample (optional)
+ *   loss_i    = (1 - alpha) * CE_smooth_i + alpha * kd_i            -> loss_per_sample (optional)
+ *   dlogits_j = [(1 - alpha) * (p_j - tgt_j) + alpha * T * (pT_j - q_j)] * gscale / B   (optional; storage dtype, columns K..ldd-1 zeroed)
+ * topk_correct (optional): the student's logits against the hard label, as atomnas_ce_smooth.  alpha == 0 gives the bits of
+ * atomnas_ce_smooth; teacher == logits bit for bit gives kd_i == 0 and the CE gradient times (1 - alpha).  Columns >= K of logits and
+ * teacher are never read. */
+int atomnas_ce_distill(const float* logits, int ldl, const float* teacher, int ldt, const long long* target, float eps, float alpha,
+                       float temperature, int B, int K, float* loss_per_sample, float* kd_per_sample, void* dlogits, int ldd,
+                       float gscale, int* topk_correct, int dtype, void* stream);
 int atomnas_colsum(const void* x, int ld, float* out, long M, int C, int dtype, void* stream);
 
 /* ---- optimizer tail on flat fp32 arenas (one launch for all parameters)

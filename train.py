@@ -279,12 +279,15 @@ def train_val_test():
     FLAGS._bn_to_prune = prune.get_bn_to_prune(model, FLAGS.prune_params, verbose=udist.is_master())
     rho_scheduler = prune.get_rho_scheduler(FLAGS.prune_params, FLAGS._steps_per_epoch)
     clip_norm, skip_nonfinite = mc.guard_options()   # a bad value stops the run here, before anything is captured
+    distill = mc.distill_options()                   # so does a bad `distill:` block
+    teacher = mc.get_teacher()                       # None without the block; validation, shrink and checkpoints see the student only
+    distill_kw = dict(teacher=teacher, distill_alpha=distill['alpha'], distill_temperature=distill['temperature']) if distill else {}
     step = engine.TrainStep(model, optimizer, ema, FLAGS._bn_to_prune, weight_decay=FLAGS.weight_decay,
                             wd_method=FLAGS.weight_decay_method, label_smoothing=FLAGS.label_smoothing,
                             batch_size=FLAGS.per_gpu_batch_size, image_size=FLAGS.image_size,
                             world_size=udist.get_world_size_fallback(),
                             allreduce_bn=bool(FLAGS.use_distributed and FLAGS.get('allreduce_bn', False)), accum_steps=mc.grad_accum_steps(),
-                            clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
+                            clip_norm=clip_norm, skip_nonfinite=skip_nonfinite, **distill_kw)
     guard_seen = [0, FLAGS._global_step]   # the guard's skipped counter and the global step at the last check
 
     def check_guard(where):
@@ -325,9 +328,12 @@ def train_val_test():
                 st = check_guard('log interval') if step.guarded else None
                 if udist.is_master():
                     ce, l2, l1 = step.loss.tolist()   # the only host synchronisation of the interval
+                    kd = float(step.kd) if step.kd is not None else None   # distilling: `loss` is the combined objective, kd its soft term
                     dt = time.time() - t0
                     line = 'Epoch {}/{} step {} loss {:.4f} l2 {:.4f} l1 {:.4f} lr {:.5f} {:.0f} img/s/GPU'.format(
                         epoch, FLAGS.num_epochs, FLAGS._global_step, ce, l2, l1, optimizer.param_groups[0]['lr'], seen / dt)
+                    if kd is not None:
+                        line += ' kd {:.4f}'.format(kd)
                     if st is not None:
                         line += ' gnorm {:.4f} skipped {} clipped {}'.format(st['norm'], st['skipped'], st['clipped'])
                     logging.info(line)
