@@ -469,8 +469,9 @@ class TrainStep:
 
     def reset_accumulation(self):
         """discards a partial group: the next accumulate() starts from zero.  The running statistics are already back at their values
-        of the start of the step (every fold leaves them there); the dropout counter steps back to where the group began."""
-        if self._pending and not self.mgr.dirty and self.mgr.version == self._group_version:
+        of the start of the step (every fold leaves them there); the dropout counter steps back to where the group began (also across an
+        arena rebuild: the counter survives one, runtime.ArenaManager._bind)."""
+        if self._pending:
             ops.add_i64(self.mgr.step_counter, -self._pending)
         self._pending = 0
 

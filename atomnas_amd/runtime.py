@@ -366,6 +366,8 @@ class ArenaManager:
         self.P = self.G = self.SQ = self.BUF = self.EMA = self.S = self.SEMA = self.CNT = None
         self._stats_ws, self._stats_off, self._stats_need = None, 0, 0
         self.version = 0
+        self.step_counter = None   # device int64[1]: the dropout / stochastic-depth counter, one per micro-batch ever drawn
+        self._counter_start = 0    # its value at the first materialisation (set_step_counter before the arenas exist: a resumed run)
         self.param_slots = collections.OrderedDict()  # name -> (off, shape, strides) of every nn.Parameter
         self.compute_dtype = getattr(model, "compute_dtype", torch.bfloat16)
 
@@ -382,6 +384,13 @@ class ArenaManager:
 
     def mark_dirty(self):
         self.dirty = True
+
+    def set_step_counter(self, value):
+        """The dropout counter of a run that continues another one (train.resume_run): the number of micro-batches drawn so far.  Works
+        before the first materialisation (the arenas then start from it) and after it (the tensor captured graphs read is kept)."""
+        self._counter_start = int(value)
+        if self.step_counter is not None:
+            self.step_counter.fill_(int(value))
 
     def ensure(self):
         if self.dirty:
@@ -532,7 +541,12 @@ class ArenaManager:
         self.hyper_host[4] = 1.0
         self._hyper_ring = torch.zeros(64, 8, dtype=torch.float32).pin_memory()  # staging slots: the host may run ahead
         self._hyper_slot = 0
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)  # decorrelates dropout masks across iterations
+        # decorrelates dropout masks across iterations.  It counts the micro-batches of the RUN: a rebuild (a shrink) carries it over, so
+        # the steps after one do not draw the masks of steps 0, 1, 2, ... again
+        old = self.step_counter
+        self.step_counter = torch.full((1,), self._counter_start, dtype=torch.int64, device=dev)
+        if old is not None:
+            self.step_counter.copy_(old)
         self.bn_trained = False
         self._depth = 0
         self.dirty = False

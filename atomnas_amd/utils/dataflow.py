@@ -735,6 +735,11 @@ class DecodedLoader(object):
     def __len__(self):
         return self.per_rank // self.batch_size if self.drop_last else (self.per_rank + self.batch_size - 1) // self.batch_size
 
+    def set_epoch(self, epoch):
+        """DistributedSampler.set_epoch (the reference's train.py:155): the next pass is pass `epoch` of a fresh loader, and the passes
+        after it count on from there.  Without a call the passes are counted from the loader's construction."""
+        self.epoch = int(epoch)
+
     def _indices(self):
         n = len(self.dset)
         if self.shuffle:

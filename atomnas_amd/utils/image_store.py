@@ -240,6 +240,10 @@ class ResidentLoader(object):
     def __len__(self):
         return self.per_rank // self.batch_size if self.drop_last else (self.per_rank + self.batch_size - 1) // self.batch_size
 
+    def set_epoch(self, epoch):
+        """as DecodedLoader.set_epoch: the next pass is pass `epoch` of a fresh loader"""
+        self.epoch = int(epoch)
+
     def _indices(self):
         n = len(self.dset)
         if self.shuffle:

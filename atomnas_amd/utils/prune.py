@@ -33,6 +33,21 @@ class PruneInfo(object):
     def penalty(self):
         return self.get_info_list('penalty')
 
+    # -- checkpoint: the penalties are normalised over the atoms of the network get_bn_to_prune saw (the supernet of the run's start)
+    # and a shrink re-inserts re-keyed names, so neither the values nor the order can be recomputed from a shrunk network
+    def penalty_state(self):
+        return [[n, v['penalty']] for n, v in self._info.items()]
+
+    def load_penalty_state(self, pairs):
+        """order and penalties of a checkpointed run over the same gammas; everything else (per_channel_flops, masks) stays"""
+        names = [n for n, _ in pairs]
+        if sorted(names) != sorted(self._info):
+            raise ValueError('the checkpoint penalises other BatchNorm weights than this model has: {} vs {}'.format(
+                sorted(set(names) ^ set(self._info))[:4], len(self._info)))
+        for n, p in pairs:
+            self._info[n]['penalty'] = p
+        self._info = collections.OrderedDict((n, self._info[n]) for n in names)
+
     # -- dynamic shrinkage protocol
     def compress_start(self):
         for v in self._info.values():

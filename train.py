@@ -252,6 +252,55 @@ def load_checkpoint(ckpt, model_wrapper, optimizer, ema):
     return ckpt['last_epoch'], ckpt['best_val']
 
 
+def optimizer_steps_per_epoch():
+    """optimizer steps the training loop takes per epoch: `max_steps_per_epoch` where the yaml shortens the epochs, else the epoch of
+    the schedules (FLAGS._steps_per_epoch, which the learning-rate and rho schedules keep measuring in)"""
+    FLAGS = cfg.FLAGS
+    return FLAGS.get('max_steps_per_epoch', None) or FLAGS._steps_per_epoch
+
+
+def checkpoint_state(model_wrapper, optimizer, ema, epoch, best_val, results):
+    """The checkpoint dict in the reference's format (utils/common.py:123-137) plus what a resumed run needs to compute what the
+    uninterrupted one would: the optimizer's parameter order by name (load_checkpoint), the global step, the dropout counter, and the
+    order and penalties of the prune table (normalised over the supernet the run started from, re-keyed by every shrink)."""
+    import common as mc
+    from atomnas_amd import runtime
+    FLAGS = cfg.FLAGS
+    pname = {id(p): n for n, p in model_wrapper.named_parameters()}
+    counter = runtime.manager_of(mc.unwrap_model(model_wrapper)).step_counter
+    prune_info = FLAGS.get('_bn_to_prune', None)
+    return {'model': {k: v.detach().clone() for k, v in model_wrapper.state_dict().items()}, 'optimizer': optimizer.state_dict(),
+            'optimizer_param_names': [pname[id(p)] for p in optimizer.param_groups[0]['params']],
+            'ema': ema.state_dict() if ema else None, 'last_epoch': epoch, 'best_val': min(best_val, results['top1_error']),
+            # the reference's resume unpacks `train_meters, val_meters = checkpoint['meters']` (train.py:313): a pair
+            'meters': (None, None),
+            'global_step': int(FLAGS._global_step), 'dropout_counter': int(counter) if counter is not None else 0,
+            'prune_penalty': prune_info.penalty_state() if prune_info is not None else None}
+
+
+def resume_run(ckpt, model_wrapper, optimizer, ema, lr_scheduler, prune_info=None):
+    """Continues the run that wrote `ckpt` -> (last_epoch, best_val): load_checkpoint, then the bookkeeping that is not a tensor of the
+    model, the optimizer or the EMA -- the global step (FLAGS._global_step, the scheduler's last_epoch: they drive the learning rate,
+    rho and the EMA warm-up), the dropout counter and the prune table.  A checkpoint without the additional keys (the reference's,
+    or an older one of ours) derives them: optimizer steps per epoch x epochs done, x micro-batches per step for the counter."""
+    import common as mc
+    from atomnas_amd import runtime
+    FLAGS = cfg.FLAGS
+    last_epoch, best_val = load_checkpoint(ckpt, model_wrapper, optimizer, ema)
+    global_step = ckpt.get('global_step')
+    if global_step is None:
+        global_step = (last_epoch + 1) * optimizer_steps_per_epoch()
+    lr_scheduler.last_epoch = global_step
+    FLAGS._global_step = global_step
+    counter = ckpt.get('dropout_counter')
+    if counter is None:
+        counter = global_step * mc.grad_accum_steps()
+    runtime.manager_of(mc.unwrap_model(model_wrapper)).set_step_counter(counter)
+    if prune_info is not None and ckpt.get('prune_penalty') is not None:
+        prune_info.load_penalty_state(ckpt['prune_penalty'])
+    return last_epoch, best_val
+
+
 def train_val_test():
     import common as mc
     FLAGS = cfg.FLAGS
@@ -269,14 +318,12 @@ def train_val_test():
     lr_scheduler = optim.get_lr_scheduler(optimizer, FLAGS)
     last_epoch, best_val = -1, 1.0
     FLAGS._global_step = 0
+    assert FLAGS.profiling, '`m.macs` is used for calculating penalty'
+    mc.profiling(model)   # (shapes only: nothing runs, so it may precede the checkpoint)
+    FLAGS._bn_to_prune = prune.get_bn_to_prune(model, FLAGS.prune_params, verbose=udist.is_master())
     if FLAGS.resume:
         ckpt = torch.load(os.path.join(FLAGS.resume, 'latest_checkpoint.pt'), map_location='cpu', weights_only=False)
-        last_epoch, best_val = load_checkpoint(ckpt, model_wrapper, optimizer, ema)
-        lr_scheduler.last_epoch = (last_epoch + 1) * FLAGS._steps_per_epoch
-        FLAGS._global_step = (last_epoch + 1) * FLAGS._steps_per_epoch
-    assert FLAGS.profiling, '`m.macs` is used for calculating penalty'
-    mc.profiling(model)
-    FLAGS._bn_to_prune = prune.get_bn_to_prune(model, FLAGS.prune_params, verbose=udist.is_master())
+        last_epoch, best_val = resume_run(ckpt, model_wrapper, optimizer, ema, lr_scheduler, FLAGS._bn_to_prune)
     rho_scheduler = prune.get_rho_scheduler(FLAGS.prune_params, FLAGS._steps_per_epoch)
     clip_norm, skip_nonfinite = mc.guard_options()   # a bad value stops the run here, before anything is captured
     distill = mc.distill_options()                   # so does a bad `distill:` block
@@ -302,15 +349,17 @@ def train_val_test():
     accum = step.accum_steps   # loader batches per optimizer step; _steps_per_epoch / max_steps_per_epoch count optimizer steps
     val_criterion = optim.CrossEntropyLabelSmooth(FLAGS.model_kwparams['num_classes'], 0.0, reduction='none')
     val_meters = mc.get_meters('val')
-    steps_per_epoch = FLAGS.get('max_steps_per_epoch', None) or FLAGS._steps_per_epoch
+    steps_per_epoch = optimizer_steps_per_epoch()
     rank = udist.get_rank_fallback()
     for epoch in range(last_epoch + 1, FLAGS.num_epochs):
         model.train()
         t0, seen = time.time(), 0
+        for loader in (LOADERS[:2] if LOADERS is not None else ()):   # the shuffle of epoch k, whether or not the run started at 0
+            if hasattr(loader, 'set_epoch'):                            # (train.py:155 / val.py:36 of the reference)
+                loader.set_epoch(epoch)
         batches = (device_batches(LOADERS[0], steps_per_epoch * accum) if LOADERS is not None else
                    fake_batches(FLAGS.per_gpu_batch_size, FLAGS.image_size, FLAGS.model_kwparams['num_classes'], steps_per_epoch * accum,
                                 FLAGS.get('random_seed', 0) + rank + 1000 * epoch))
-        step.reset_accumulation()   # a trailing partial group of the last epoch is dropped, as a short last batch is
         for x, y in batches:
             if x.shape[0] != FLAGS.per_gpu_batch_size:
                 continue   # a short last batch: the captured step has a static batch (drop_last: True avoids drawing it)
@@ -337,6 +386,9 @@ def train_val_test():
                     if st is not None:
                         line += ' gnorm {:.4f} skipped {} clipped {}'.format(st['norm'], st['skipped'], st['clipped'])
                     logging.info(line)
+        # a trailing partial group of the epoch is dropped, as a short last batch is -- here, so that the shrink and the checkpoint below
+        # see the dropout counter of the whole steps only
+        step.reset_accumulation()
         if step.guarded:
             check_guard('end of epoch {}'.format(epoch))
         results, eval_wrapper = validate(epoch, model_wrapper, ema, val_criterion, val_meters, FLAGS.get('val_steps', 4))
@@ -355,12 +407,7 @@ def train_val_test():
         if udist.is_master() and FLAGS.get('log_dir', None):
             os.makedirs(FLAGS.log_dir, exist_ok=True)
             kw = mb.output_network(model)
-            pname = {id(p): n for n, p in model_wrapper.named_parameters()}
-            state = {'model': {k: v.detach().clone() for k, v in model_wrapper.state_dict().items()}, 'optimizer': optimizer.state_dict(),
-                     'optimizer_param_names': [pname[id(p)] for p in optimizer.param_groups[0]['params']],
-                     'ema': ema.state_dict() if ema else None, 'last_epoch': epoch, 'best_val': min(best_val, results['top1_error']),
-                     # the reference's resume unpacks `train_meters, val_meters = checkpoint['meters']` (train.py:313): a pair
-                     'meters': (None, None)}
+            state = checkpoint_state(model_wrapper, optimizer, ema, epoch, best_val, results)
             torch.save(state, os.path.join(FLAGS.log_dir, 'latest_checkpoint.pt'))
             with open(os.path.join(FLAGS.log_dir, 'latest_checkpoint.yml'), 'w') as f:
                 f.write(str(kw))
